@@ -7,6 +7,12 @@ A step = one hipGraph replay of forward + decode + NMS over the batch, plus (N>1
 one RCCL all-gather of the per-image [det | count] records (ydbl.parallel).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model n|s|l] [--batch B] [--imgsz S] [--fp32]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (images/s, ms_per_step).
+--dump-outputs DIR also writes what the last timed step computed (det, count) as DIR/<name>.npy.
+--full adds the measurements that take runs of their own: the per-launch roofline and the CPU baseline
+with its mAP@0.5 check (each can still be left out with --no-roofline / --no-cpu-baseline).
 
 N>1: launched by torch.distributed.run, one process per GPU; weak scaling
 (B images per GPU), max-over-ranks time, value = all images / time.
@@ -411,7 +417,7 @@ def stub_step_factory(B: int, world: int, rank: int):
     det, cnt = record_views(rec, 300)
     det.fill_(float(rank))
     cnt.fill_(rank + 1)
-    out = torch.empty(world * B, rec.shape[1])
+    out = torch.empty(world * B, rec.shape[1]) if world > 1 else rec  # world 1: no collective, the records are it
     glob = GlobalDetections(out, B * world, world, 300)
 
     def step():
@@ -420,6 +426,7 @@ def stub_step_factory(B: int, world: int, rank: int):
             d, c = glob.tensors()
             assert d.shape[0] == B * world and int(c[-1]) == world and float(d[-1, 0, 0]) == world - 1
 
+    step.glob = glob
     return step
 
 
@@ -442,8 +449,15 @@ def main():
                     help="time the public API instead of the session: each step is YOLO.predict(batch, half=...) on "
                          "the HBM-resident batch (LoadTensor checks + copy into the session's input buffer, the "
                          "same split hipGraph, the per-batch count sync, Results objects); no roofline / CPU legs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-launch roofline and the CPU baseline with its "
+                         "mAP@0.5 check (runs of their own; `roofline` and `cpu_baseline` of the line are null without it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed, as a caller of the timed path receives it "
+                         "(det [images, max_det, 6] with the rows past each image's count zeroed, count [images]), "
+                         "to DIR/<name>.npy as float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave the roofline out")
     ap.add_argument("--stub-cpu", action="store_true", help="gloo/CPU plumbing check of the N-rank launch (no GPU)")
     args = ap.parse_args()
 
@@ -496,6 +510,9 @@ def main():
         sp.run()  # forward + decode + NMS (one hipGraph replay, the sub-batch plans as its branches) [+ the one all-gather]
 
     el = timed_steps(step, args, world, lambda: torch.cuda.synchronize(dev), dev)
+    if rank == 0 and args.dump_outputs:  # what ShardedPredictor.__call__ returns for the step just run
+        det, count = (sess.det, sess.count) if world == 1 else sp.global_dets.tensors()
+        dump_outputs(args.dump_outputs, det, count)
     key = workload_key(args, dtype_name)
     if rank == 0 and os.environ.get("YDBL_WORKLOAD_KEY_OUT"):  # scripts/pmc_families.sh
         Path(os.environ["YDBL_WORKLOAD_KEY_OUT"]).write_text(key)
@@ -505,7 +522,7 @@ def main():
     if args.fp8:  # achieved share of the candidate MACs in e4m3 (output-pixel MACs, ydbl.quant.candidate_macs)
         extra["fp8_mac_fraction"] = round(float(sess.fp8_mac_fraction), 4)
     rf = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # The roofline describes the kernels at the headline launch size: one launch per layer over the
         # whole per-GPU batch.  With --streams k the timed run splits that batch into k concurrent
         # sub-batch graphs, whose launches overlap; the per-launch view is taken on the full-batch plan.
@@ -522,7 +539,7 @@ def main():
         rf = roofline(rsess, dtype_name, key=rkey, step_ms=el * 1e3 / args.steps)
         rf["plan"] = f"full-batch plan (bs {B}, one launch per layer); timed run on {args.streams} stream(s)"
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.model, S, B, gpu_session=(model, fp8, half))
     if rank == 0:
         emit_line(args, world, el, dtype_name, cfg, extra, rf, cpu)
@@ -556,6 +573,12 @@ def predict_main(args, model, world, rank, dev, half, fp8, dtype_name, cfg):
         out["r"] = model.predict(x, **kw)
 
     el = timed_steps(step, args, world, lambda: torch.cuda.synchronize(dev), dev)
+    if rank == 0 and args.dump_outputs:  # this rank's Results (predict() has no collective), padded to max_det rows
+        boxes = [r.boxes.data.float() for r in out["r"]]
+        det = torch.zeros((B, 300, 6), device=dev)
+        for i, b in enumerate(boxes):
+            det[i, : len(b)] = b
+        dump_outputs(args.dump_outputs, det, torch.tensor([len(b) for b in boxes], device=dev))
     if rank == 0:
         extra = {"dets_per_image": round(sum(len(r.boxes.data) for r in out["r"]) / B, 2),
                  "via": "YOLO.predict(x, half=%s) per step (Results construction included; the detections are read "
@@ -586,6 +609,31 @@ def timed_steps(step, args, world, sync, dev=None) -> float:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = t.item()
     return el
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, det, count):
+    """--dump-outputs: det [n, max_det, 6] and count [n] of the last timed step as DIR/det.npy and DIR/count.npy
+    (float32).  Rows of det past an image's count are not part of the result (the NMS leaves them as they were)
+    and are written as zeros.  Above 64 MB in all, a fixed seeded sample of the images is written instead, with
+    their indices in DIR/images.npy."""
+    import numpy as np
+
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    det, count = det.detach().float().cpu(), count.detach().cpu().long()
+    keep = torch.arange(det.shape[1])[None, :] < count[:, None]
+    det = torch.where(keep[:, :, None], det, torch.zeros(()))
+    per_image = (det[0].numel() + 2) * 4
+    if det.shape[0] * per_image > DUMP_LIMIT_BYTES:
+        idx = torch.randperm(det.shape[0], generator=torch.Generator().manual_seed(0))[: DUMP_LIMIT_BYTES // per_image]
+        idx = idx.sort().values
+        det, count = det[idx], count[idx]
+        np.save(d / "images.npy", idx.numpy().astype(np.float32))
+    np.save(d / "det.npy", det.numpy().astype(np.float32))
+    np.save(d / "count.npy", count.numpy().astype(np.float32))
 
 
 def emit_line(args, world, el, dtype_name, cfg, extra, rf, cpu):
@@ -621,6 +669,8 @@ def stub_main(args, world, rank):
         assert dist.get_world_size() == args.gpus
     step = stub_step_factory(args.batch, world, rank)
     el = timed_steps(step, args, world, lambda: None)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, *step.glob.tensors())
     if rank == 0:
         emit_line(args, world, el, "stub", CFGS[args.model][0], {"stub": "gloo/CPU plumbing, no GPU work"}, None, None)
     if world > 1:

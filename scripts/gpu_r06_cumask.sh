@@ -6,5 +6,5 @@ timeout -k 10 300 python -u scripts/cu_mask_probe.py --model n --batch 32 > $T/c
 grep -v amdgpu $T/cumask_n32.txt
 timeout -k 10 300 python -u scripts/cu_mask_probe.py --model s --batch 8 > $T/cumask_s8.txt 2>&1 || { tail -20 $T/cumask_s8.txt; exit 1; }
 grep -v amdgpu $T/cumask_s8.txt
-timeout -k 10 300 python bench.py > $T/bench.log 2>&1 || { tail -20 $T/bench.log; exit 1; }
+timeout -k 10 300 python bench.py --full > $T/bench.log 2>&1 || { tail -20 $T/bench.log; exit 1; }
 tail -1 $T/bench.log | cut -c1-600

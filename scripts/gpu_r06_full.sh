@@ -7,7 +7,7 @@ timeout -k 10 900 python -u -m pytest tests -q -m gpu --timeout 300 --timeout-me
 tail -2 $T/pytest_gpu.txt
 run() {  # name, bench args...
   local n=$1; shift
-  timeout -k 10 300 python bench.py "$@" > $T/$n.json.log 2>&1 || { echo "bench $n failed"; tail -20 $T/$n.json.log; exit 1; }
+  timeout -k 10 300 python bench.py --full "$@" > $T/$n.json.log 2>&1 || { echo "bench $n failed"; tail -20 $T/$n.json.log; exit 1; }
   tail -1 $T/$n.json.log > $T/$n.json
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $T/prof_$n -o run -- python bench.py --steps 20 --warmup 5 \
       --no-cpu-baseline --no-roofline "$@" > $T/prof_$n.log 2>&1 || { echo "rocprof $n failed"; tail -20 $T/prof_$n.log; exit 1; }

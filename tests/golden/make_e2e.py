@@ -49,6 +49,27 @@ def choose_conf(y64):
     return float(f"{torch.quantile(sc, 0.995).item():.3g}")
 
 
+FILE_LIMIT = 1 << 20  # no committed file above 1 MiB
+
+
+def save_e2e(out, name, y64, d32, meta):
+    """e2e_<name>.npz = {y64, d32, meta} when that stays within FILE_LIMIT; else {d32, meta, y64_parts} with y64
+    beside it as e2e_<name>.y64_<i>.npz, split by image into parts of at most FILE_LIMIT raw bytes (read back by
+    parity_util.load_e2e)."""
+    import io
+
+    buf = io.BytesIO()
+    np.savez_compressed(buf, y64=y64, d32=d32, meta=meta)
+    if len(buf.getvalue()) <= FILE_LIMIT:
+        (out / f"e2e_{name}.npz").write_bytes(buf.getvalue())
+        return
+    per = max(1, FILE_LIMIT // y64[0].nbytes)
+    parts = [y64[i:i + per] for i in range(0, len(y64), per)]
+    for i, p in enumerate(parts):
+        np.savez_compressed(out / f"e2e_{name}.y64_{i}.npz", y64=p)
+    np.savez_compressed(out / f"e2e_{name}.npz", d32=d32, meta=meta, y64_parts=np.array(len(parts)))
+
+
 def main(names=None):
     for name, (scale, S, B, ref) in CASES.items():
         if names and name not in names:
@@ -70,7 +91,7 @@ def main(names=None):
                        "det_pairs": m["pairs"], "det_box_dev": m["box_dev"], "det_conf_dev": m["conf_dev"]})
             meta[f"oracle_{leg}"] = st
         d32 = (ys["fp32"].double() - y64).half().numpy()
-        np.savez_compressed(OUT / f"e2e_{name}.npz", y64=y64.float().numpy(), d32=d32, meta=np.array(json.dumps(meta)))
+        save_e2e(OUT, name, y64.float().numpy(), d32, np.array(json.dumps(meta)))
         print(name, {k: round(v, 2) for k, v in secs.items()}, json.dumps(meta))
 
 

@@ -101,7 +101,12 @@ def load_e2e(golden_dir, name):
     import numpy as np
 
     with np.load(golden_dir / f"e2e_{name}.npz", allow_pickle=False) as z:
-        y64 = torch.from_numpy(z["y64"]).double()
+        if "y64" in z.files:
+            y = z["y64"]
+        else:  # a fixture above 1 MiB keeps y64 beside it, split by image (tests/golden/make_e2e.py save_e2e)
+            y = np.concatenate([np.load(golden_dir / f"e2e_{name}.y64_{i}.npz", allow_pickle=False)["y64"]
+                                for i in range(int(z["y64_parts"]))])
+        y64 = torch.from_numpy(y).double()
         meta = json.loads(str(z["meta"]))
         if "d32" in z.files:
             meta["y32"] = y64 + torch.from_numpy(z["d32"]).double()
