@@ -1,7 +1,7 @@
 """A/B of YDBL_* routing knobs on the bench workload in ONE process (same box, interleaved rounds), so box-to-box
 spread does not enter the comparison.  Each variant is a separate session (the session key holds the knobs).
 
-    python scripts/ab_bench.py "A:" "B:YDBL_CV3_FUSE=1;YDBL_NO_MERGE=1" [--model n] [--batch 32] [--streams 2] [--rounds 5]
+    python scripts/ab_bench.py "A:" "B:YDBL_HALO_NB=1;YDBL_NO_MERGE=1" [--model n] [--batch 32] [--streams 2] [--rounds 5]
     python scripts/ab_bench.py "S2:" "S3:STREAMS=3" "S4:STREAMS=4"        (sub-batch graphs per variant)
 A variant listed twice under two names ("A:" ... "A2:") is two sessions with the same routing: their spread is the
 session-to-session bias (buffer placement), about 0.5 % on DBL-n bs32 (profiles/r06/r06_defaults_ab.txt).

@@ -287,16 +287,15 @@ def test_conv_tile(dtype, cin, cout, s, h, w, res):
     (1, 64, 128, 200, 256, None),     # two output-channel splits
     (2, 256, 48, 170, 152, "add"),    # Cout not a multiple of 16
     (32, 384, 64, 40, 40, None),      # DBL-n head Bottleneck cv1 (deep Cin, 40-wide map: ragged column tile)
-    (2, 64, 96, 256, 256, None),      # 16-row tiles, partial second output-channel split
+    (2, 64, 96, 256, 256, None),      # partial second output-channel split
     (2, 320, 80, 160, 176, "add"),    # deep Cin (> 256) on a map large enough for the halo path
     (16, 384, 64, 40, 40, None),      # bs16 sub-batch head conv: < 400 workgroups -> 32-channel slices
     (16, 192, 48, 40, 40, "add"),     # 32-channel slices, partial second slice, residual
 ])
 def test_conv3x3_halo(dtype, n, cin, cout, h, w, res, monkeypatch):
-    """3x3 stride-1 convs with Cin >= 64 on >= 25600 output pixels: the halo-tiled kernel (8/16-row tiles,
-    64- or 32-channel slices; YDBL_HALO_T16=1 and YDBL_HALO_NB=1 so the 16-row and one-image forms stay covered --
-    the default N-blocked form has test_conv3x3_halo_nblock)."""
-    monkeypatch.setenv("YDBL_HALO_T16", "1")
+    """3x3 stride-1 convs with Cin >= 64 on >= 25600 output pixels: the halo-tiled kernel (8-row tiles,
+    64- or 32-channel slices; YDBL_HALO_NB=1 so the one-image form stays covered -- the default N-blocked form
+    has test_conv3x3_halo_nblock)."""
     monkeypatch.setenv("YDBL_HALO_NB", "1")
     from ydbl import _lib
     from ydbl.nn.modules import emit_dense
@@ -1192,12 +1191,18 @@ def test_dsconv_lean_bit_identical(case, monkeypatch):
     torch.testing.assert_close(outs[0][0], ref, rtol=3e-2, atol=3e-2)
 
 
-@pytest.mark.parametrize("c,n,shape,sliced", [(64, 2, (16, 64, 40, 40), False), (64, 1, (3, 64, 13, 21), True),
-                                              (128, 2, (4, 128, 20, 20), True)])
-def test_dsc3k_cv3_fused_bit_identical(c, n, shape, sliced, monkeypatch):
-    """DSC3k (U/nn/modules/block.py:1447-1503, C3 with DSBottlenecks k3 -> k7, e = 1): cv3 as the trailing GEMM of
-    the last bottleneck's k7 DSConv (ydbl_dsconv_desc.g2: the bottleneck output stays on the CU) == the separate
-    k7 DSConv + cv3 launches, bit for bit; one launch fewer; close to the oracle."""
+# a DSC3k with two DSBottlenecks (k3 -> k7): (C-ABI entry, Step.what) of every launch, in order
+DSC3K_N2_STEPS = [("ydbl_conv2d_nhwc", "Conv1x1x2"),
+                  ("ydbl_dsconv_nhwc", "DSConv.k3s1"), ("ydbl_dsconv_nhwc", "DSConv.k7s1"),
+                  ("ydbl_dsconv_nhwc", "DSConv.k3s1"), ("ydbl_dsconv_nhwc", "DSConv.k7s1"),
+                  ("ydbl_conv2d_nhwc", "Conv1x1")]
+
+
+@pytest.mark.parametrize("c,n,shape,sliced", [(64, 1, (3, 64, 13, 21), True), (64, 2, (2, 64, 9, 7), True),
+                                              (128, 2, (4, 128, 20, 20), True), (64, 2, (16, 64, 40, 40), False)])
+def test_dsc3k_matches_oracle(c, n, shape, sliced):
+    """DSC3k (U/nn/modules/block.py:1447-1503, C3 with DSBottlenecks k3 -> k7, e = 1) is close to the oracle, and
+    its plan is the merged cv2 | cv1 1x1, one launch per DSConv and cv3: a re-fusion or a split shows here."""
     from oracle import model as om
     from ydbl.nn import modules as M
     from ydbl.utils.synthetic import trained_like_
@@ -1205,98 +1210,19 @@ def test_dsc3k_cv3_fused_bit_identical(c, n, shape, sliced, monkeypatch):
     torch.manual_seed(c + n + shape[2])
     o = trained_like_(om.DSC3k(c, c, n, True, e=1.0, k1=3, k2=7), seed=c).eval()
     x = torch.randn(*shape)
-    outs, nsteps = [], []
-    monkeypatch.setenv("YDBL_CV1_FUSE", "0")  # the leading-1x1 fusion has its own test (below)
-    for fuse in ("1", ""):
-        if fuse:
-            monkeypatch.setenv("YDBL_CV3_FUSE", "1")
-        else:
-            monkeypatch.setenv("YDBL_CV3_FUSE", "0")
-        pm = M.DSC3k(c, c, n, True, e=1.0, k1=3, k2=7)
-        pm.load_state_dict(o.state_dict())
-        plan = _plan(torch.float16)
-        xv = _tv_from_nchw(plan, x)
-        ybuf = plan.alloc(shape[0], shape[2], shape[3], c + (24 if sliced else 0))
-        yv = ybuf.cslice(8, c) if sliced else ybuf
-        pm.emit(plan, xv, yv)
-        nsteps.append(len(plan.steps))
-        assert any("+cv3" in st.what for st in plan.steps) == bool(fuse)
-        _run(plan)
-        outs.append(yv.nchw().float().cpu())
-    assert nsteps[0] == nsteps[1] - 1
-    assert torch.equal(outs[0], outs[1]), (outs[0] - outs[1]).abs().max()
-    with torch.no_grad():
-        ref = o(x)
-    torch.testing.assert_close(outs[0], ref, rtol=3e-2, atol=3e-2)
-
-
-@pytest.mark.parametrize("n,shape,sliced", [(2, (16, 64, 40, 40), False), (1, (3, 64, 13, 21), True),
-                                            (2, (2, 64, 9, 7), True)])
-def test_dsc3k_cv1_fused_bit_identical(n, shape, sliced, monkeypatch):
-    """DSC3k at c_ = 64: the merged cv2 | cv1 1x1 as the leading GEMM of the first bottleneck's k3 DSConv
-    (ydbl_dsconv_desc.g0: cv1's map recomputed on the tile halo, zero outside the image, both 1x1 outputs still
-    written) == the separate 1x1 + k3 DSConv launches, bit for bit; one launch fewer; close to the oracle."""
-    from oracle import model as om
-    from ydbl.nn import modules as M
-    from ydbl.utils.synthetic import trained_like_
-
-    c = 64
-    torch.manual_seed(n + shape[2])
-    o = trained_like_(om.DSC3k(c, c, n, True, e=1.0, k1=3, k2=7), seed=7).eval()
-    x = torch.randn(*shape)
-    outs, nsteps = [], []
-    monkeypatch.setenv("YDBL_CV3_FUSE", "1")  # the leading 1x1 rides only in the trailing-GEMM layout (C3.emit)
-    for fuse in ("1", ""):
-        if fuse:
-            monkeypatch.setenv("YDBL_CV1_FUSE", "1")
-        else:
-            monkeypatch.setenv("YDBL_CV1_FUSE", "0")
-        pm = M.DSC3k(c, c, n, True, e=1.0, k1=3, k2=7)
-        pm.load_state_dict(o.state_dict())
-        plan = _plan(torch.float16)
-        xv = _tv_from_nchw(plan, x)
-        ybuf = plan.alloc(shape[0], shape[2], shape[3], c + (24 if sliced else 0))
-        yv = ybuf.cslice(8, c) if sliced else ybuf
-        pm.emit(plan, xv, yv)
-        nsteps.append(len(plan.steps))
-        assert any(st.what.startswith("Conv1x1x2+") for st in plan.steps) == bool(fuse)
-        _run(plan)
-        outs.append(yv.nchw().float().cpu())
-    assert nsteps[0] == nsteps[1] - 1
-    assert torch.equal(outs[0], outs[1]), (outs[0] - outs[1]).abs().max()
-    with torch.no_grad():
-        ref = o(x)
-    torch.testing.assert_close(outs[0], ref, rtol=3e-2, atol=3e-2)
-
-
-def test_dsconv_g0_rejects_bad_descriptors():
-    """ydbl_dsconv_nhwc with a leading 1x1 (g0) refuses, before launching anything, descriptors whose x is not
-    the last x.c channels of g0_y, whose channel counts are not (64 -> 128, x.c 64), or that add a residual."""
-    import ctypes
-
-    from ydbl import _lib
-
+    pm = M.DSC3k(c, c, n, True, e=1.0, k1=3, k2=7)
+    pm.load_state_dict(o.state_dict())
     plan = _plan(torch.float16)
-    n, h, w = 1, 8, 8
-    x0 = plan.alloc(n, h, w, 64)
-    buf = plan.alloc(n, h, w, 192)
-    y0, x, y = buf.cslice(64, 128), buf.cslice(128, 64), plan.alloc(n, h, w, 64)
-    dww = torch.zeros(9 * 64, device=DEV)
-    pww = torch.zeros(64 * 64, dtype=torch.float16, device=DEV)
-    bias = torch.zeros(128, device=DEV)
-    w0 = torch.zeros(128 * 64, dtype=torch.float16, device=DEV)
-    nv = _lib.View(None, 0, 0, 0, 0, 0, 0)
-
-    def desc(xv, y0v, res=None):
-        return _lib.DsConvDesc(xv.struct(), y.struct(), res.struct() if res is not None else nv, dww.data_ptr(),
-                               pww.data_ptr(), bias.data_ptr(), 3, 1, 1, 1, 64, _lib.ACT_SILU,
-                               _lib.RES_ADD if res is not None else _lib.RES_NONE, None, 0, None, None, nv, 0,
-                               None, None, nv, nv, 0, w0.data_ptr(), bias.data_ptr(), x0.struct(), y0v.struct(),
-                               _lib.ACT_SILU)
-    for d in (desc(buf.cslice(64, 64), y0),        # x is the first half of g0_y, not its last channels
-              desc(x, buf.cslice(64, 96)),          # g0_y.c != 2 x.c
-              desc(x, y0, res=y)):                  # no residual with g0
-        assert _lib.lib.ydbl_dsconv_nhwc(ctypes.byref(d), None) != 0
+    xv = _tv_from_nchw(plan, x)
+    ybuf = plan.alloc(shape[0], shape[2], shape[3], c + (24 if sliced else 0))
+    yv = ybuf.cslice(8, c) if sliced else ybuf
+    pm.emit(plan, xv, yv)
+    if n == 2:
+        assert [(st.fn.__name__, st.what) for st in plan.steps] == DSC3K_N2_STEPS
+    _run(plan)
+    with torch.no_grad():
+        ref = o(x)
+    torch.testing.assert_close(yv.nchw().float().cpu(), ref, rtol=3e-2, atol=3e-2)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16])

@@ -24,14 +24,17 @@
 
 namespace ydbl {
 
+// Output rows per tile.  (16-row tiles, weights staged once per 256 pixels, measured even to +0.7 % behind the N-blocked
+// 8-row tiles in the two-branch layout and were removed: profiles/r06/r06_conv_route_sweep.txt.)
+constexpr int HALO_TH = 8;
 
 // NB > 1 (N-blocking): the workgroup takes the same tile of NB consecutive images, so every staged weight chunk feeds NB
 // times the MFMAs (the weights are most of a deep-K chunk's bytes: 384->64 @40^2, 8-row tile, 64 channels: 36.9 KB
 // of weights against 11.5 KB of halo per 32-channel chunk).
-template <typename T, int S, int TH, int NTN, bool Q8, int NB = 1>
+template <typename T, int S, int NTN, bool Q8, int NB = 1>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvArgs<T> p, int tiles_x, int tiles_y,
                                                               int co_splits) {
-  constexpr int TW = 16;
+  constexpr int TH = HALO_TH, TW = 16;
   constexpr int VEC = Vec<T>::N;
   constexpr int BK = 4 * VEC;
   constexpr int IH = (TH - 1) * S + 3, IW = (TW - 1) * S + 3;
@@ -214,10 +217,10 @@ int halo_ksplit(const ConvArgs<T>& a, int64_t wgs) {
   return k;
 }
 
-template <typename T, bool Q8, int S, int TH>
+template <typename T, bool Q8, int S>
 static void launch_halo(const ConvArgs<T>& a0, hipStream_t s) {
   ConvArgs<T> a = a0;
-  const int tiles_x = (int)cdiv(a.Wo, 16), tiles_y = (int)cdiv(a.Ho, TH);
+  const int tiles_x = (int)cdiv(a.Wo, 16), tiles_y = (int)cdiv(a.Ho, HALO_TH);
   const int64_t ntiles = (int64_t)a.N * tiles_y * tiles_x;
   a.ksplit = 1;
   if (S == 1 && (int64_t)a.P < 25600) {  // (the split's own tiling: 32-channel slices below)
@@ -225,7 +228,7 @@ static void launch_halo(const ConvArgs<T>& a0, hipStream_t s) {
     if (a.ksplit > 1 && (!a.ws || a.ws_bytes < (int64_t)a.ksplit * a.P * ((a.Cout + 3) & ~3) * 4)) a.ksplit = 1;
     if (a.ksplit > 1) {
       const int cs = (int)cdiv(a.Cout, 32);
-      conv3x3_halo_kernel<T, S, TH, 2, Q8><<<dim3((unsigned)(ntiles * cs), (unsigned)a.ksplit), 256, 0, s>>>(
+      conv3x3_halo_kernel<T, S, 2, Q8><<<dim3((unsigned)(ntiles * cs), (unsigned)a.ksplit), 256, 0, s>>>(
           a, tiles_x, tiles_y, cs);
       launch_splitk_epilogue<T, Q8>(a, s);
       return;
@@ -242,24 +245,24 @@ static void launch_halo(const ConvArgs<T>& a0, hipStream_t s) {
   // +0.8 %, DBL-s bs64 / DBL-l 1280 bs8 +0.4 %, DBL-s bs8 even (profiles/r06/r06_fusion_switch_sweep.txt,
   // r06_sweep2.txt; per launch in graph at bs16: 384->64 @40^2 28.3 -> 33.5 us, 192->64 17.6 -> 20.2).
   // YDBL_HALO_NB=1 (read per launch; A/B switch): one image per workgroup.
-  if constexpr (S == 1 && TH == 8 && !Q8) {
+  if constexpr (S == 1 && !Q8) {
     // (four images per workgroup, or two in 64-channel slices: DBL-n bs32 -3.1 / -2.3 %, r06_sweep3_cumask.txt)
     const char* e = getenv("YDBL_HALO_NB");
     if (!(e && *e == '1') && a.N >= 2) {
       const int64_t nt2 = (int64_t)(a.N + 1) / 2 * tiles_y * tiles_x;
       const int cs = (int)cdiv(a.Cout, 32);
-      conv3x3_halo_kernel<T, S, TH, 2, Q8, 2><<<(unsigned)(nt2 * cs), 256, 0, s>>>(a, tiles_x, tiles_y, cs);
+      conv3x3_halo_kernel<T, S, 2, Q8, 2><<<(unsigned)(nt2 * cs), 256, 0, s>>>(a, tiles_x, tiles_y, cs);
       return;
     }
   }
   if (a.Cout <= 32) {
-    conv3x3_halo_kernel<T, S, TH, 2, Q8><<<(unsigned)ntiles, 256, 0, s>>>(a, tiles_x, tiles_y, 1);
+    conv3x3_halo_kernel<T, S, 2, Q8><<<(unsigned)ntiles, 256, 0, s>>>(a, tiles_x, tiles_y, 1);
   } else if (ntiles * cdiv(a.Cout, 64) < n2_below) {
     const int cs = (int)cdiv(a.Cout, 32);
-    conv3x3_halo_kernel<T, S, TH, 2, Q8><<<(unsigned)(ntiles * cs), 256, 0, s>>>(a, tiles_x, tiles_y, cs);
+    conv3x3_halo_kernel<T, S, 2, Q8><<<(unsigned)(ntiles * cs), 256, 0, s>>>(a, tiles_x, tiles_y, cs);
   } else {
     const int cs = (int)cdiv(a.Cout, 64);
-    conv3x3_halo_kernel<T, S, TH, 4, Q8><<<(unsigned)(ntiles * cs), 256, 0, s>>>(a, tiles_x, tiles_y, cs);
+    conv3x3_halo_kernel<T, S, 4, Q8><<<(unsigned)(ntiles * cs), 256, 0, s>>>(a, tiles_x, tiles_y, cs);
   }
 }
 
@@ -271,8 +274,6 @@ static void launch_halo(const ConvArgs<T>& a0, hipStream_t s) {
 // Where the halo tile beats the implicit GEMM (scripts/conv_bench.py, fp16, MI355X): stride 1 on
 // >= 51200 output pixels.  Measured: 256->32 @80^2 bs32 132 -> 62 us, 512->64 @80^2 bs64
 // 714 -> 382 us, 768->128 @40^2 bs64 534 -> 348 us, 1024->128 @160^2 bs8 1371 -> 688 us.
-// 16-row tiles where the map allows (weights staged once per 256 pixels instead of 128),
-// 4-row tiles when 8-row tiles would leave fewer than 512 workgroups.
 template <typename T, bool Q8>
 bool try_conv3x3_halo(const ConvArgs<T>& a, int kh, hipStream_t s) {
   constexpr int BK = 4 * Vec<T>::N;
@@ -281,7 +282,7 @@ bool try_conv3x3_halo(const ConvArgs<T>& a, int kh, hipStream_t s) {
   // 17.8 vs 24.7 us, and DBL-n's 64->64 @80 bs32 (18.8 vs 17.5 us alone) cost the whole step ~40 us.
   if (kh == 3 && a.KW == 3 && a.PAD == 1 && a.DIL == 1 && a.S == 2 && a.Cin % BK == 0 &&
       a.Cin >= 2 * BK && a.xcs % Vec<T>::N == 0 && (int64_t)a.P >= 204800)
-    return launch_halo<T, Q8, 2, 8>(a, s), true;
+    return launch_halo<T, Q8, 2>(a, s), true;
   if (kh != 3 || a.KW != 3 || a.PAD != 1 || a.DIL != 1 || a.S != 1) return false;
   if (a.Cin % BK || a.Cin < 2 * BK || a.xcs % Vec<T>::N) return false;
   // 51200 output pixels (40^2 x 32) was the measured crossover at bs32; the bench's two bs16 sub-batch
@@ -291,31 +292,19 @@ bool try_conv3x3_halo(const ConvArgs<T>& a, int kh, hipStream_t s) {
     const int64_t wgs = (int64_t)a.N * cdiv(a.Ho, 8) * cdiv(a.Wo, 16) * cdiv(a.Cout, 32);
     const int k = halo_ksplit(a, wgs);
     if ((int64_t)a.P < 4096) return false;
-    if (k >= 2 && a.ws && a.ws_bytes >= (int64_t)k * a.P * ((a.Cout + 3) & ~3) * 4) return launch_halo<T, Q8, 1, 8>(a, s), true;
+    if (k >= 2 && a.ws && a.ws_bytes >= (int64_t)k * a.P * ((a.Cout + 3) & ~3) * 4) return launch_halo<T, Q8, 1>(a, s), true;
     // Too few chunks to split (Cin < 256) and wide Cout: the wave-split-K kernel's 32x128 tiles would re-read the
     // whole weight matrix once per 32 pixels (DBL-s bs4: 128->256 @40^2, 200 tile rows x 590 KB); the halo tile in
     // 32-channel slices reads it once per 128 pixels
     // (YDBL_HALO_SMALL=0, read per launch: the wave-split-K route, A/B switch)
     const char* e = getenv("YDBL_HALO_SMALL");
-    if (k < 2 && a.Cout >= 128 && !(e && *e == '0')) return launch_halo<T, Q8, 1, 8>(a, s), true;
+    if (k < 2 && a.Cout >= 128 && !(e && *e == '0')) return launch_halo<T, Q8, 1>(a, s), true;
     return false;
   }
-  const int64_t csplit = cdiv(a.Cout, 64);
-  const int64_t tiles8 = (int64_t)a.N * cdiv(a.Ho, 8) * cdiv(a.Wo, 16) * csplit;
-  const int64_t tiles16 = (int64_t)a.N * cdiv(a.Ho, 16) * cdiv(a.Wo, 16) * csplit;
-  // No 4-row tiles by default: every workgroup re-reads all of its channels' weights, so at 480
-  // 8-row tiles (40^2 bs32, Cout 64) the doubled grid lost (A/B: 384->64 88.9 vs
-  // 49.6 us, 192->64 45.9 vs 28.0 us); 384->64 @40^2 also beats the wave-split-K kernel it used to
-  // take (78.8 us).  (P >= 51200 already guarantees >= 400 8-row tiles.)
-  (void)tiles8;
-  // Cout <= 32 (one 32-channel slice: the weights are as many bytes per chunk as the halo): 16-row tiles from
-  // 256 of them (DBL-n's 256->32 @80^2 at bs16, 400 tiles: 34.6 -> 31.8 us in graph, scripts/kbench.py)
-  // 16-row tiles only with YDBL_HALO_T16=1 (read per launch): the N-blocked 8-row tiles measured even to +0.7 % against
-  // them in the two-branch layout (profiles/r06/r06_conv_route_sweep.txt)
-  const char* e16 = getenv("YDBL_HALO_T16");
-  if (a.Ho % 16 == 0 && (a.Cout > 32 ? tiles16 >= 512 : tiles16 >= 256) && e16 && *e16 == '1')
-    launch_halo<T, Q8, 1, 16>(a, s);
-  else launch_halo<T, Q8, 1, 8>(a, s);
+  // No 4-row tiles: every workgroup re-reads all of its channels' weights, so at 480 8-row tiles (40^2 bs32,
+  // Cout 64) the doubled grid lost (A/B: 384->64 88.9 vs 49.6 us, 192->64 45.9 vs 28.0 us); 384->64 @40^2 also
+  // beats the wave-split-K kernel it used to take (78.8 us).
+  launch_halo<T, Q8, 1>(a, s);
   return true;
 }
 

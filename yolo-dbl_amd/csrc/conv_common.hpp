@@ -26,14 +26,6 @@ struct ConvArgs {
   // y3[p][k] = sum_c t3w[k][c] * T(y[p][c]) + t3b[k]
   const float* t3w; const float* t3b;
   T* y3; int y3cs; int nt3;
-  // optional trailing GEMM over [y ; g2x] (dsc_lean.hip, C3's cv3): g2y = g2act(g2w [y ; g2x] + g2b), y not stored
-  const T* g2w; const float* g2b;
-  const T* g2x; int g2xcs;
-  T* g2y; int g2ycs; int g2act;
-  // optional leading 1x1 (dsc_lean.hip, C3's merged cv2|cv1): g0y = g0act(g0w g0x + g0b), x = g0y's last Cin channels
-  const T* g0w; const float* g0b;
-  const T* g0x; int g0xcs;
-  T* g0y; int g0ycs; int g0act;
   // split-K (conv_wsk_kernel): ksplit > 1 -> fp32 partial tiles ws[z][P][round_up(Cout, 4)], summed + epilogue by
   // splitk_epilogue_kernel
   float* ws; int64_t ws_bytes; int ksplit;

@@ -23,36 +23,32 @@
 
 namespace ydbl {
 
-template <int C, int CO, int K, int S, int TH, int TW, int NT, bool TG = false, bool TAIL = false, bool PRE = false>
+template <int C, int CO, int K, int S, int TH, int TW, int NT, bool TAIL>
 __global__ __launch_bounds__(NT, 1) void dsc_lean_kernel(ConvArgs<_Float16> p, const float* __restrict__ dww,
                                                           const float* __restrict__ dwb, int dw_act, int tiles_x,
                                                           int tiles_y, int ntiles) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[LeanLds<C, CO, K, S, TH, TW, NT, TG, PRE, TAIL>::BYTES];
-  lean_tile<C, CO, K, S, TH, TW, NT, TG, TAIL, PRE>(p, dww, dwb, dw_act, xcd_remap(blockIdx.x, ntiles), tiles_x,
-                                                          tiles_y, smem);
+  __shared__ __attribute__((aligned(16))) unsigned char smem[LeanLds<C, CO, K, S, TH, TW, NT, TAIL>::BYTES];
+  lean_tile<C, CO, K, S, TH, TW, NT, TAIL>(p, dww, dwb, dw_act, xcd_remap(blockIdx.x, ntiles), tiles_x, tiles_y, smem);
 }
 
-template <int C, int CO, int K, int S, int TH, int TW, int NT, bool TG, bool TAIL, bool PRE = false>
+template <int C, int CO, int K, int S, int TH, int TW, int NT, bool TAIL>
 static void lean_go2(const ConvArgs<_Float16>& a, const float* dww, const float* dwb, int dw_act, hipStream_t s) {
   const int tiles_x = (int)cdiv(a.Wo, TW), tiles_y = (int)cdiv(a.Ho, TH);
   const int ntiles = a.N * tiles_y * tiles_x;
   // (measured and not kept: a persistent walk with the next tile's halo prefetched -- 2-3 workgroups per CU,
   // VGPR-bound, slower or even on every DBL-n shape but the 80^2 stride-2 one, which the chunked kernel takes)
-  dsc_lean_kernel<C, CO, K, S, TH, TW, NT, TG, TAIL, PRE><<<(unsigned)ntiles, NT, 0, s>>>(a, dww, dwb, dw_act, tiles_x,
-                                                                                     tiles_y, ntiles);
+  dsc_lean_kernel<C, CO, K, S, TH, TW, NT, TAIL><<<(unsigned)ntiles, NT, 0, s>>>(a, dww, dwb, dw_act, tiles_x, tiles_y,
+                                                                                  ntiles);
 }
 
 // the Detect class-conv tail (p.t3w, CO 64 only) as its own instance: its 64 tail weights per lane would
 // otherwise set the register budget of every launch of the shape
-template <int C, int CO, int K, int S, int TH, int TW, int NT, bool TG = false>
+template <int C, int CO, int K, int S, int TH, int TW, int NT>
 static void lean_go(const ConvArgs<_Float16>& a, const float* dww, const float* dwb, int dw_act, hipStream_t s) {
-  if constexpr (CO == 64 && !TG) {
-    if (a.t3w) return lean_go2<C, CO, K, S, TH, TW, NT, TG, true>(a, dww, dwb, dw_act, s);
+  if constexpr (CO == 64) {
+    if (a.t3w) return lean_go2<C, CO, K, S, TH, TW, NT, true>(a, dww, dwb, dw_act, s);
   }
-  if constexpr (C == 64 && CO == 64 && K == 3 && S == 1 && !TG) {
-    if (a.g0w) return lean_go2<C, CO, K, S, TH, TW, NT, TG, false, true>(a, dww, dwb, dw_act, s);
-  }
-  lean_go2<C, CO, K, S, TH, TW, NT, TG, false>(a, dww, dwb, dw_act, s);
+  lean_go2<C, CO, K, S, TH, TW, NT, false>(a, dww, dwb, dw_act, s);
 }
 
 constexpr int64_t LEAN_MAX_TILES_WIDE = 160;
@@ -67,19 +63,11 @@ bool try_dsc_lean(const ConvArgs<_Float16>& a, const float* dww, const float* dw
   if (a.xcs % 8 || a.ycs % 4 || (a.res && a.rcs % 4) || a.KPAD != a.Cin) return false;
   const int c = a.Cin, co = a.Cout;
   if (a.t3w && co != 64) return false;
-  if (a.g0w && !(st == 1 && k == 3 && c == 64 && co == 64)) return false;  // the leading 1x1 (ydbl.h g0)
   // 128+ input channels only while the map is small enough that the chunked kernel cannot fill the chip
   // (<= 160 8x8 tiles: DBL-n's 20^2 maps at bs16).  On DBL-s bs64 (800 tiles at 40^2) and DBL-l 1280
   // (400 tiles at 80^2) the lean kernel's 512-thread one-round-trip tiles lost to the chunked kernel:
-  // +43 / +35 ms over the bench's profile run (profiles/r03/r03rec_c{3,4}_*).  Must agree with
-  // ydbl.nn.modules.C3._cv3_fusable (the trailing GEMM exists only here).
+  // +43 / +35 ms over the bench's profile run (profiles/r03/r03rec_c{3,4}_*).
   if (c >= 128 && lean_tiles8(a) > LEAN_MAX_TILES_WIDE) return false;
-  if (a.g2w) {  // DSC3k's last bottleneck k7 DSConv + its cv3 (ydbl.h: g2)
-    if (st != 1 || k != 7 || c != co || a.g2xcs % 8 || a.g2ycs % 4) return false;
-    if (c == 64) return lean_go<64, 64, 7, 1, 8, 8, 256, true>(a, dww, dwb, dw_act, s), true;
-    if (c == 128) return lean_go<128, 128, 7, 1, 8, 8, 512, true>(a, dww, dwb, dw_act, s), true;
-    return false;
-  }
   if (st == 1 && k == 3) {
     if (c == 64 && co == 64) return lean_go<64, 64, 3, 1, 8, 8, 256>(a, dww, dwb, dw_act, s), true;
     if (c == 128 && co == 128) return lean_go<128, 128, 3, 1, 8, 8, 512>(a, dww, dwb, dw_act, s), true;

@@ -7,23 +7,21 @@ namespace ydbl {
 __device__ __forceinline__ int lean_bswz(int row, int kv) { return row * 4 + (kv ^ (((row >> 2) & 1) << 1)); }
 
 // LDS carve-up of one lean tile
-template <int C, int CO, int K, int S, int TH, int TW, int NT, bool TG, bool PRE, bool TAIL = false>
+template <int C, int CO, int K, int S, int TH, int TW, int NT, bool TAIL = false>
 struct LeanLds {
   static constexpr int IH = (TH - 1) * S + K, IW = (TW - 1) * S + K, IWP = IW | 1, NQ = C / 4;
-  static constexpr int NPX = TH * TW, NKS = C / 32, PNP = PRE ? (IH * IW + 15) / 16 * 16 : 16;
+  static constexpr int NPX = TH * TW, NKS = C / 32;
   static constexpr int X = 0;                                              // h4 [IH * IWP * NQ]
   static constexpr int W = (X + IH * IWP * NQ * 8 + 15) / 16 * 16;          // f32x4 [K * K * NQ]
   static constexpr int B = W + K * K * NQ * 16;                             // h8 [NKS * NPX * 4]
-  static constexpr int P = B + NKS * NPX * 4 * 16;                          // h8 [2 * PNP * 4] (PRE)
-  static constexpr int T = P + (PRE ? 2 * PNP * 4 * 16 : 16);               // f32 [4][CO] class-conv weights (TAIL)
+  static constexpr int T = B + NKS * NPX * 4 * 16;                          // f32 [4][CO] class-conv weights (TAIL)
   static constexpr int BI = T + (TAIL ? 4 * CO * 4 : 0);                    // f32 [CO] pointwise bias
-  static constexpr int BI2 = BI + CO * 4;                                   // f32 [CO] trailing-GEMM bias (TG)
-  static constexpr int BYTES = BI2 + (TG ? CO * 4 : 0);
+  static constexpr int BYTES = BI + CO * 4;
 };
 
 // One TH x TW output tile (linear tile index `tile`: image-major, then tile row, tile column).
 // smem: LeanLds::BYTES of LDS, 16-byte aligned.
-template <int C, int CO, int K, int S, int TH, int TW, int NT, bool TG, bool TAIL, bool PRE>
+template <int C, int CO, int K, int S, int TH, int TW, int NT, bool TAIL>
 __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const float* __restrict__ dww,
                                           const float* __restrict__ dwb, int dw_act, int tile, int tiles_x,
                                           int tiles_y, unsigned char* smem) {
@@ -52,21 +50,10 @@ __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const flo
   static_assert(NTC % TN == 0 && WAVES % NCG == 0, "channel groups over waves");
   constexpr int WPG = WAVES / NCG;
   constexpr int TM = (NTP + WPG - 1) / WPG;          // pixel tiles per wave
-  // TG: trailing GEMM over [y ; g2x] (2*CO channels, CO/16 output tiles as the pointwise): its B tile
-  // [2*CO/32 k-steps][pixel][slot] reuses the halo's LDS once the depthwise phase is over
-  constexpr int NKS2 = TG ? 2 * CO / 32 : 0;
-  static_assert(!TG || (C == CO && NKS2 * NPX * 4 * 16 <= IH * IWP * NQ * 8), "trailing GEMM layout");
-  constexpr int X2V = TG ? NPX * CO / 8 : 1, X2IT = (X2V + NT - 1) / NT;
-  // PRE: leading 1x1 g0y = act(W0 g0x + b0) (2C outputs: C3's cv2 | cv1) over the whole halo, its last C channels
-  // are this DSConv's input; B tile [2 k-steps][halo pixel, padded to 16][slot], one 16-channel tile pair per wave
-  static_assert(!PRE || (C == 64 && CO == 64 && S == 1 && !TG && !TAIL && WAVES == 4), "leading 1x1 layout");
-  constexpr int PNP = PRE ? (IH * IW + 15) / 16 * 16 : 16, PNT = PNP / 16;
-  using L = LeanLds<C, CO, K, S, TH, TW, NT, TG, PRE, TAIL>;
+  using L = LeanLds<C, CO, K, S, TH, TW, NT, TAIL>;
   h4* s_x = reinterpret_cast<h4*>(smem + L::X);      // fp16 halo, [row][col][quad]
   f32x4* s_w = reinterpret_cast<f32x4*>(smem + L::W);  // fp32 taps (rounded to fp16), [tap][quad]
   h8* s_b = reinterpret_cast<h8*>(smem + L::B);      // pointwise B tile, [k-step][pixel][slot]
-  h8* s_g = reinterpret_cast<h8*>(s_x);              // TG: trailing GEMM B tile (after the depthwise phase)
-  h8* s_p = reinterpret_cast<h8*>(smem + L::P);      // PRE: the leading 1x1's B tile (g0x halo)
   // activation accessors (element offsets from each view's base)
   auto ld16 = [&](const T* base, int64_t off, bool ok) -> h8 { return vload_sel(base + off, base, ok); };
   auto ld8 = [&](const T* base, int64_t off) -> h4 { return *reinterpret_cast<const h4*>(base + off); };
@@ -97,8 +84,6 @@ __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const flo
     return tl;
   };
   h8 xr[HIT];
-  const T* xsrc = PRE ? p.g0x : p.x;
-  const int xscs = PRE ? p.g0xcs : p.xcs;
   auto load_halo = [&](const Tile& tl) {
 #pragma unroll
     for (int it = 0; it < HIT; ++it) {
@@ -107,11 +92,11 @@ __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const flo
       const int hy = px / IW, hx = px - hy * IW;
       const int iy = tl.iy0 + hy, ix = tl.ix0 + hx;
       const bool ok = iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-      xr[it] = ld16(xsrc, ((int64_t)(tl.b * p.H + iy) * p.W + ix) * xscs + cv * 8, ok);
+      xr[it] = ld16(p.x, ((int64_t)(tl.b * p.H + iy) * p.W + ix) * p.xcs + cv * 8, ok);
     }
   };
 
-  // ---- 1. one round trip: halo + taps (-> LDS), then A fragments (+ residual, second GEMM input) (-> VGPRs)
+  // ---- 1. one round trip: halo + taps (-> LDS), then A fragments (+ residual) (-> VGPRs)
   const Tile tl = tile_of(tile);
   load_halo(tl);
   f32x4 wr[TIT];
@@ -122,18 +107,14 @@ __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const flo
 #pragma unroll
     for (int e = 0; e < 4; ++e) wr[it][e] = float(T(w[e]));  // the reference's .half() weights
   }
-  // the pointwise bias (+ TG's g2b, + TAIL's class-conv weights [k][CO]) for LDS: loaded here, in the first round
-  // trip, and stored just before its barrier (a store right after its load waits on every load issued before it).
+  // the pointwise bias (+ TAIL's class-conv weights [k][CO]) for LDS: loaded here, in the first round trip,
+  // and stored just before its barrier (a store right after its load waits on every load issued before it).
   // Read from global after the MFMAs they cost one more round trip at the very end; kept in VGPRs from the start
   // they cost 16 registers and a wave per SIMD.
   constexpr int BIT = (CO + NT - 1) / NT, TLT = TAIL ? (4 * CO + NT - 1) / NT : 0;
-  float bir[BIT], b2r[TG ? BIT : 1], tlr[TLT > 0 ? TLT : 1];
+  float bir[BIT], tlr[TLT > 0 ? TLT : 1];
 #pragma unroll
-  for (int it = 0; it < BIT; ++it) {
-    const int i = min(tid + it * NT, CO - 1);
-    bir[it] = p.bias[i];
-    if constexpr (TG) b2r[it] = p.g2b[i];
-  }
+  for (int it = 0; it < BIT; ++it) bir[it] = p.bias[min(tid + it * NT, CO - 1)];
 #pragma unroll
   for (int it = 0; it < TLT; ++it) {
     const int i = min(tid + it * NT, 4 * CO - 1);
@@ -145,21 +126,6 @@ __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const flo
     const int row = (cg * TN + i) * 16 + r16;  // A rows: output channel of this lane
 #pragma unroll
     for (int m = 0; m < NKS; ++m) af[i][m] = vload(p.w + (int64_t)row * p.KPAD + m * 32 + g * 8);
-  }
-
-  // PRE: tile i = 0 of this wave = 16 channels of the cv1 half (C + 16 wave.., over the whole halo, before the
-  // depthwise), i = 1 = 16 channels of the cv2 half (16 wave.., over the output pixels only, after the pointwise)
-  h8 a0[2][2];
-  float b0v[2][4];
-  if constexpr (PRE) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int ct = i == 0 ? C / 16 + wave : wave;
-      const int row = ct * 16 + r16;
-#pragma unroll
-      for (int m = 0; m < 2; ++m) a0[i][m] = vload(p.g0w + (int64_t)row * C + m * 32 + g * 8);
-      load_f<4>(p.g0b + ct * 16 + 4 * g, b0v[i]);
-    }
   }
 #pragma unroll
   for (int it = 0; it < TIT; ++it)
@@ -175,17 +141,6 @@ __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const flo
       pv[j] = pt < NTP && oy < p.Ho && ox < p.Wo;
       pp[j] = pv[j] ? ((int64_t)tl.b * p.Ho + oy) * p.Wo + ox : 0;
     }
-    h8 x2r[X2IT];  // TG: the second GEMM input's tile (C3's cv2 branch), [pixel][8-channel vector]
-    if constexpr (TG) {
-#pragma unroll
-      for (int it = 0; it < X2IT; ++it) {
-        const int i = min(tid + it * NT, X2V - 1);
-        const int px = i / (CO / 8), cv = i % (CO / 8);
-        const int oy = tl.oy0 + px / TW, ox = tl.ox0 + px % TW;
-        const bool ok = oy < p.Ho && ox < p.Wo;
-        x2r[it] = ld16(p.g2x, (((int64_t)tl.b * p.Ho + oy) * p.Wo + ox) * p.g2xcs + cv * 8, ok);
-      }
-    }
     h4 rv[TN][TM];
     if (p.res != YDBL_RES_NONE) {
 #pragma unroll
@@ -198,56 +153,17 @@ __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const flo
       const int i = tid + it * NT;
       if (i < HV) {
         const int cv = i % CV, px = i / CV;
-        if constexpr (PRE) {
-          s_p[(cv >> 2) * PNP * 4 + lean_bswz(px, cv & 3)] = xr[it];
-        } else {
-          const int hy = px / IW, hx = px - hy * IW;
-          *reinterpret_cast<h8*>(&s_x[(hy * IWP + hx) * NQ + cv * 2]) = xr[it];
-        }
-      }
-    }
-    if constexpr (PRE) {  // the pad pixels of the last 16-pixel tile: finite zeros (never stored)
-      for (int i = tid; i < (PNP - IH * IW) * CV; i += NT) {
-        const int cv = i % CV, px = IH * IW + i / CV;
-        s_p[(cv >> 2) * PNP * 4 + lean_bswz(px, cv & 3)] = h8{0, 0, 0, 0, 0, 0, 0, 0};
+        const int hy = px / IW, hx = px - hy * IW;
+        *reinterpret_cast<h8*>(&s_x[(hy * IWP + hx) * NQ + cv * 2]) = xr[it];
       }
     }
 #pragma unroll
     for (int it = 0; it < BIT; ++it)
-      if (tid + it * NT < CO) {
-        reinterpret_cast<float*>(smem + L::BI)[tid + it * NT] = bir[it];
-        if constexpr (TG) reinterpret_cast<float*>(smem + L::BI2)[tid + it * NT] = b2r[it];
-      }
+      if (tid + it * NT < CO) reinterpret_cast<float*>(smem + L::BI)[tid + it * NT] = bir[it];
 #pragma unroll
     for (int it = 0; it < TLT; ++it)
       if (tid + it * NT < 4 * CO) reinterpret_cast<float*>(smem + L::T)[tid + it * NT] = tlr[it];
     __syncthreads();
-    if constexpr (PRE) {
-      // ---- 1b. leading 1x1 over the halo on MFMA (k-steps in channel order, epilogue as conv_epilogue's):
-      // every output pixel's 2C values -> g0y; the last C channels (zero outside the image: the depthwise
-      // padding) -> the fp16 halo in LDS, exactly what the unfused DSConv would read back
-      const int c = C + wave * 16 + 4 * g;
-#pragma unroll
-      for (int j = 0; j < PNT; ++j) {
-        f32x4 pa = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-          pa = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[0][m], s_p[m * PNP * 4 + lean_bswz(j * 16 + r16, g)], pa, 0, 0, 0);
-        const int px = j * 16 + r16;
-        const int hy = px / IW, hx = px - hy * IW;
-        const int iy = tl.iy0 + hy, ix = tl.ix0 + hx;
-        const bool live = px < IH * IW;
-        const bool inimg = live && iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;
-        const bool outpx = inimg && hy >= p.PAD && hy < p.PAD + TH && hx >= p.PAD && hx < p.PAD + TW;
-        float v[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = apply_act<T>(pa[q] + b0v[0][q], p.g0act);
-        const h4 o = to_h4_rne(v);
-        if (outpx) *reinterpret_cast<h4*>(p.g0y + ((int64_t)(tl.b * p.H + iy) * p.W + ix) * p.g0ycs + c) = o;
-        if (live) s_x[(hy * IWP + hx) * NQ + (c - C) / 4] = inimg ? o : h4{0, 0, 0, 0};
-      }
-      __syncthreads();
-    }
 
     // ---- 2. depthwise: task = (quad q, output row r, segment sg), quad fastest
     {
@@ -336,93 +252,15 @@ __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const flo
 #pragma unroll
           for (int q = 0; q < 4; ++q) v[q] = float(rv[i][j][q]) * v[q];
         }
-        if constexpr (TG) {  // y (rounded as the unfused path stores it) -> the trailing GEMM's B tile
-          const int px = (wp + WPG * j) * 16 + r16, c = co[i];
-          *(reinterpret_cast<h4*>(&s_g[(c >> 5) * NPX * 4 + lean_bswz(px, (c >> 3) & 3)]) + ((c >> 2) & 1)) =
-              to_h4_rne(v);
-        } else {
-          st8(p.y, pp[j] * p.ycs + co[i], v);
-          if constexpr (TAIL) {
+        st8(p.y, pp[j] * p.ycs + co[i], v);
+        if constexpr (TAIL) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) ys[i][j][q] = round_to<T>(v[q]);
-          }
+          for (int q = 0; q < 4; ++q) ys[i][j][q] = round_to<T>(v[q]);
         }
       }
     }
-    if constexpr (PRE) {
-      // ---- 3b. the cv2 half of the leading 1x1 over the output pixels (s_p is read-only since the first barrier)
-      const int c = wave * 16 + 4 * g;
-#pragma unroll
-      for (int j = 0; j < NTP; ++j) {
-        const int op = j * 16 + r16;
-        const int hpx = (op / TW + p.PAD) * IW + op % TW + p.PAD;
-        f32x4 pa = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-          pa = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0[1][m], s_p[m * PNP * 4 + lean_bswz(hpx, g)], pa, 0, 0, 0);
-        const int oy = tl.oy0 + op / TW, ox = tl.ox0 + op % TW;
-        if (oy < p.Ho && ox < p.Wo) {
-          float v[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) v[q] = apply_act<T>(pa[q] + b0v[1][q], p.g0act);
-          st8(p.g0y, (((int64_t)tl.b * p.Ho + oy) * p.Wo + ox) * p.g0ycs + c, v);
-        }
-      }
-    }
-    if constexpr (TAIL && NCG == 1 && TN == 4 && !TG) {  // Detect class conv over the 64 output channels (CO == 64)
+    if constexpr (TAIL && NCG == 1 && TN == 4) {  // Detect class conv over the 64 output channels (CO == 64)
       conv_tail_1x1_vals<T, TN, TM>(p, ys, pp, pv, co, g, reinterpret_cast<const float*>(smem + L::T));
-    }
-    if constexpr (TG) {
-      // ---- 4. trailing GEMM: g2y = act(W2 [y ; g2x] + b2), K = 2*CO in channel order (the unfused cv3's k-steps)
-#pragma unroll
-      for (int it = 0; it < X2IT; ++it) {
-        const int i = tid + it * NT;
-        if (i < X2V) {
-          const int px = i / (CO / 8), cv = i % (CO / 8);
-          s_g[(CO / 32 + cv / 4) * NPX * 4 + lean_bswz(px, cv & 3)] = x2r[it];
-        }
-      }
-      h8 a2[TN][NKS2];
-#pragma unroll
-      for (int i = 0; i < TN; ++i) {
-        const int row = (cg * TN + i) * 16 + r16;
-#pragma unroll
-        for (int m = 0; m < NKS2; ++m) a2[i][m] = vload(p.g2w + (int64_t)row * (2 * CO) + m * 32 + g * 8);
-      }
-      float b2v[TN][4];
-#pragma unroll
-      for (int i = 0; i < TN; ++i) {
-        const f32x4 b4 = *reinterpret_cast<const f32x4*>(smem + L::BI2 + co[i] * 4);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) b2v[i][q] = b4[q];
-      }
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int j = 0; j < TM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int m = 0; m < NKS2; ++m)
-#pragma unroll
-        for (int j = 0; j < TM; ++j) {
-          const int pt = wp + WPG * j;
-          if (TM * WPG == NTP || pt < NTP) {
-            const h8 bf = s_g[m * NPX * 4 + lean_bswz(pt * 16 + r16, g)];
-#pragma unroll
-            for (int i = 0; i < TN; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a2[i][m], bf, acc[i][j], 0, 0, 0);
-          }
-        }
-#pragma unroll
-      for (int j = 0; j < TM; ++j) {
-        if (!pv[j]) continue;
-#pragma unroll
-        for (int i = 0; i < TN; ++i) {
-          float v[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) v[q] = apply_act<T>(acc[i][j][q] + b2v[i][q], p.g2act);
-          st8(p.g2y, pp[j] * p.g2ycs + co[i], v);
-        }
-      }
     }
   }
 }
