@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string>
 #include <type_traits>
 
@@ -235,6 +236,7 @@ __device__ __forceinline__ float silu_fast(float v) {
   return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-v * 1.4426950408889634f));
 }
 __device__ __forceinline__ float silu_exact(float v) { return v / (1.0f + expf(-v)); }
+// Runtime dispatch on the activation code, per value: the generic path of the epilogues (see with_act).
 template <typename T>
 __device__ __forceinline__ float apply_act(float v, int act) {
   switch (act) {
@@ -245,6 +247,49 @@ __device__ __forceinline__ float apply_act(float v, int act) {
     case YDBL_ACT_SIGMOID: return sigmoidf_(v);
     default: return v;
   }
+}
+
+// ---- epilogue dispatch, resolved once per wave ------------------------------------------------
+// The activation code is a wave-uniform kernel argument.  Switched on per output value it costs every value its
+// own ladder of scalar compares and taken branches around 0-5 VALU instructions (hipcc does not unswitch the
+// unrolled epilogue loops), and every kernel carries the erff / expf code of all four activations per value.
+// with_act<T>() decides once: the two codes the fp16 networks launch almost everywhere (none, SiLU) run a body
+// compiled for that code, straight-line; every other code runs the same body with the runtime switch (ACT_RT).
+// YDBL_EPI_GENERIC=1 (read per launch: tests) sends SiLU / none down the runtime path too, so one process can
+// compare the two: ConvArgs::epi_generic, or the ACT_GENERIC mark on the code of the kernels that take a bare `act`.
+constexpr int ACT_RT = -1;
+constexpr int ACT_GENERIC = 0x100;
+inline bool epi_generic() {
+  const char* e = getenv("YDBL_EPI_GENERIC");
+  return e && *e == '1';
+}
+inline int epi_act(int act) { return epi_generic() ? act | ACT_GENERIC : act; }
+template <int A>
+using ActC = std::integral_constant<int, A>;
+template <typename T, typename F>
+__device__ __forceinline__ void with_act(int act, bool generic, F&& f) {
+  if constexpr (std::is_same<T, float>::value) {
+    f(ActC<ACT_RT>{});  // the fp32 parity path stays as it is: one form, IEEE expf and division
+  } else {
+    if (!generic && act == YDBL_ACT_SILU) f(ActC<YDBL_ACT_SILU>{});
+    else if (!generic && act == YDBL_ACT_NONE) f(ActC<YDBL_ACT_NONE>{});
+    else f(ActC<ACT_RT>{});
+  }
+}
+// the activation A (a code, or ACT_RT: the runtime code `act`) of v
+template <typename T, int A>
+__device__ __forceinline__ float act_as(float v, int act) {
+  if constexpr (A == YDBL_ACT_NONE) return v;
+  else if constexpr (A == YDBL_ACT_SILU && std::is_same<T, float>::value) return silu_exact(v);
+  else if constexpr (A == YDBL_ACT_SILU) return silu_fast(v);
+  else return apply_act<T>(v, act);
+}
+// Residual add with its own rounding.  Behind the runtime switch the activation's result reaches the add through
+// a merge point; with the activation known at compile time, SiLU's last multiply and this add would contract into
+// one fma (fp-contract=fast) and the output change by an ulp.
+__device__ __forceinline__ float add_rn(float r, float v) {
+#pragma clang fp contract(off)
+  return r + v;
 }
 
 // Plain-struct view passed by value to kernels.

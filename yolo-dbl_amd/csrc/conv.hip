@@ -31,7 +31,7 @@ __device__ __forceinline__ int swz(int row, int kv) {
   else return row * 4 + (kv ^ (((row >> 2) & 1) << 1));
 }
 
-template <typename T, int BM, int BN, int WM, int WN, bool POINTWISE, bool Q8, int PF = 1>
+template <typename T, int BM, int BN, int WM, int WN, bool POINTWISE, bool Q8, int PF = 1, int KA = ACT_RT>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs<T> p) {
   constexpr int VEC = Vec<T>::N;
   constexpr int BK = 4 * VEC;
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs<T> p) {
   }
 #pragma unroll
   for (int i = 0; i < TN; ++i) co[i] = n0 + wn * TN * 16 + i * 16 + 4 * g;
-  conv_epilogue<T, TN, TM, Q8>(p, acc, pp, pv, co, s_bias, n0);
+  conv_epilogue<T, TN, TM, Q8, KA>(p, acc, pp, pv, co, s_bias, n0);
 }
 
 // Spatial-tile 3x3 conv for thin inputs (Cin <= 32, the high-resolution backbone layers).
@@ -209,7 +209,7 @@ __device__ __forceinline__ int tswz(int pix, int cv) {
   else return pix * CV + (cv ^ ((pix / (16 / CV)) & (CV - 1)));
 }
 
-template <typename T, int CIN, int S, int TH, int TW, int NTN>
+template <typename T, int CIN, int S, int TH, int TW, int NTN, int KA = ACT_RT>
 __global__ __launch_bounds__(256) void conv3x3_tile_kernel(ConvArgs<T> p, int tiles_x, int tiles_y) {
   constexpr int VEC = Vec<T>::N;
   constexpr int CV = CIN / VEC;                 // 16-byte channel vectors per pixel
@@ -315,13 +315,21 @@ __global__ __launch_bounds__(256) void conv3x3_tile_kernel(ConvArgs<T> p, int ti
   }
 #pragma unroll
   for (int i = 0; i < NTN; ++i) co[i] = i * 16 + 4 * g;
-  conv_epilogue<T, NTN, TM>(p, acc, pp, pv, co, s_bias, 0);
+  conv_epilogue<T, NTN, TM, false, KA>(p, acc, pp, pv, co, s_bias, 0);
 }
 
 template <typename T, int CIN, int S, int TH, int TW, int NTN>
 static void launch_tile(const ConvArgs<T>& a, hipStream_t s) {
   const int tiles_x = (int)cdiv(a.Wo, TW), tiles_y = (int)cdiv(a.Ho, TH);
-  conv3x3_tile_kernel<T, CIN, S, TH, TW, NTN><<<(unsigned)(a.N * tiles_y * tiles_x), 256, 0, s>>>(a, tiles_x, tiles_y);
+  const unsigned grid = (unsigned)(a.N * tiles_y * tiles_x);
+  if constexpr (sizeof(T) == 2) {  // the epilogue form is part of the kernel (conv_common.hpp, conv_epilogue)
+    const int form = epi_host_form(a);
+    if (form == YDBL_ACT_SILU)
+      return conv3x3_tile_kernel<T, CIN, S, TH, TW, NTN, YDBL_ACT_SILU><<<grid, 256, 0, s>>>(a, tiles_x, tiles_y);
+    if (form == YDBL_ACT_NONE)
+      return conv3x3_tile_kernel<T, CIN, S, TH, TW, NTN, YDBL_ACT_NONE><<<grid, 256, 0, s>>>(a, tiles_x, tiles_y);
+  }
+  conv3x3_tile_kernel<T, CIN, S, TH, TW, NTN, ACT_RT><<<grid, 256, 0, s>>>(a, tiles_x, tiles_y);
 }
 
 // 3x3 / pad 1 / dil 1, Cin in {8,16,32}, Cout <= 64 and a multiple of 4: the spatial-tile kernel.
@@ -658,6 +666,15 @@ static bool try_wsk(const ConvArgs<T>& a, bool pointwise, hipStream_t s) {
 template <typename T, bool Q8, int BM, int BN, int WM, int WN>
 static void launch_igemm(const ConvArgs<T>& a, bool pointwise, hipStream_t s) {
   dim3 grid((unsigned)cdiv(a.P, BM), (unsigned)cdiv(a.Cout, BN));
+  // the epilogue form is part of the kernel (conv_common.hpp, conv_epilogue): fp16 SiLU / no activation compiled,
+  // for the 1x1 convs (the general form of the 128x64 and 64x64 tiles would lose a wave per SIMD to it)
+  if constexpr (sizeof(T) == 2 && !Q8) {
+    const int form = pointwise ? epi_host_form(a) : ACT_RT;
+    if (form == YDBL_ACT_SILU)
+      return conv_igemm_kernel<T, BM, BN, WM, WN, true, Q8, 1, YDBL_ACT_SILU><<<grid, 256, 0, s>>>(a);
+    if (form == YDBL_ACT_NONE)
+      return conv_igemm_kernel<T, BM, BN, WM, WN, true, Q8, 1, YDBL_ACT_NONE><<<grid, 256, 0, s>>>(a);
+  }
   if (pointwise)
     conv_igemm_kernel<T, BM, BN, WM, WN, true, Q8><<<grid, 256, 0, s>>>(a);
   else
@@ -733,6 +750,7 @@ static ConvArgs<T> conv_args(const ydbl_conv_desc* d) {
   a.KW = d->kw; a.S = d->stride; a.PAD = d->pad; a.DIL = d->dil;
   a.K = d->kh * d->kw * d->x.c; a.KPAD = d->kpad;
   a.act = d->act; a.res = d->res_mode;
+  a.epi_generic = epi_generic();
   a.P = d->y.n * d->y.h * d->y.w;
   a.y2 = reinterpret_cast<T*>(d->y2.ptr); a.y2cs = d->y2.cs;
   a.r2 = reinterpret_cast<const T*>(d->r2.ptr); a.r2cs = d->r2.cs;

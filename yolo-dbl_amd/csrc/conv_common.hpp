@@ -29,6 +29,7 @@ struct ConvArgs {
   // split-K (conv_wsk_kernel): ksplit > 1 -> fp32 partial tiles ws[z][P][round_up(Cout, 4)], summed + epilogue by
   // splitk_epilogue_kernel
   float* ws; int64_t ws_bytes; int ksplit;
+  int epi_generic;  // YDBL_EPI_GENERIC=1: every epilogue takes its runtime-dispatch form (common.hpp, with_act)
 };
 
 // ---- operand policy: f16/f32 vectors, or 8-byte groups of 8 e4m3 values (fp8 MFMA) -----------
@@ -146,11 +147,15 @@ struct BiasStage {
 // pixel pp[j].  Every load is unconditional from a clamped address (bias once; the residual of a
 // pixel for all TN tiles at once) so the loads overlap; only the stores are predicated.
 // sb: the bias staged in LDS for channels sb0.. (16-byte aligned), or nullptr to load it here.
-template <typename T, int TN, int TM, bool Q8 = false>
-__device__ __forceinline__ void conv_epilogue(const ConvArgs<T>& p, const f32x4 (&acc)[TN][TM],
-                                              const int64_t (&pp)[TM], const bool (&pv)[TM], const int (&co)[TN],
-                                              const float* sb = nullptr, int sb0 = 0) {
-  const bool c4 = (p.Cout & 3) == 0;  // uniform: co..co+3 in range whenever co < Cout
+// A: the activation (a code, or ACT_RT: p.act at run time).  R: the residual mode (a code, or -1: p.res at run
+// time).  LEAN: Cout % 4 == 0 and no second output, so a lane's four channels are in range together and nothing
+// but the y store follows.  conv_epilogue() below picks the form once per wave.
+template <typename T, int TN, int TM, bool Q8, int A, int R, bool LEAN>
+__device__ __forceinline__ void conv_epilogue_as(const ConvArgs<T>& p, const f32x4 (&acc)[TN][TM],
+                                                 const int64_t (&pp)[TM], const bool (&pv)[TM], const int (&co)[TN],
+                                                 const float* sb, int sb0) {
+  const bool c4 = LEAN || (p.Cout & 3) == 0;  // uniform: co..co+3 in range whenever co < Cout
+  const int res = R < 0 ? p.res : R;
   float bv[TN][4];
 #pragma unroll
   for (int i = 0; i < TN; ++i) {
@@ -179,7 +184,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs<T>& p, const f32x4 
   for (int j = 0; j < TM; ++j) {
     const int64_t pc = pv[j] ? pp[j] : 0;
     float rv[TN][4];
-    if (p.res != YDBL_RES_NONE) {
+    if (res != YDBL_RES_NONE) {
       const T* rp = p.r + pc * p.rcs;
 #pragma unroll
       for (int i = 0; i < TN; ++i) {
@@ -193,24 +198,27 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs<T>& p, const f32x4 
     }
 #pragma unroll
     for (int i = 0; i < TN; ++i) {
+      // the compiled forms are straight-line code: without a fence per fragment the scheduler interleaves the
+      // activations of all TN x TM fragments, which cost the igemm and tile kernels 6-15 VGPRs and a wave per SIMD
+      if constexpr (A != ACT_RT) __builtin_amdgcn_sched_barrier(0);
       float v[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) v[q] = apply_act<T>(acc[i][j][q] * dqv[i][q] + bv[i][q], p.act);
-      if (p.res == YDBL_RES_ADD) {
+      for (int q = 0; q < 4; ++q) v[q] = act_as<T, A>(acc[i][j][q] * dqv[i][q] + bv[i][q], p.act);
+      if (res == YDBL_RES_ADD) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = rv[i][q] + v[q];
-      } else if (p.res == YDBL_RES_MUL) {
+        for (int q = 0; q < 4; ++q) v[q] = A == ACT_RT ? rv[i][q] + v[q] : add_rn(rv[i][q], v[q]);
+      } else if (res == YDBL_RES_MUL) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) v[q] = rv[i][q] * v[q];
       }
       if (!pv[j] || co[i] >= p.Cout) continue;
       T* yp = p.y + pc * p.ycs + co[i];
-      if (co[i] + 4 <= p.Cout) {
+      if (LEAN || co[i] + 4 <= p.Cout) {
         store_f<4>(yp, v);
       } else {
         for (int q = 0; q < 4 && co[i] + q < p.Cout; ++q) store_f<1>(yp + q, v + q);
       }
-      if (p.y2) {  // uniform
+      if (!LEAN && p.y2) {  // uniform
         const T* r2p = p.r2 + pc * p.r2cs + co[i];
         T* y2p = p.y2 + pc * p.y2cs + co[i];
         if (co[i] + 4 <= p.Cout) {
@@ -228,6 +236,42 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs<T>& p, const f32x4 
           }
         }
       }
+    }
+  }
+}
+
+// The form of the epilogue, decided once per wave from the wave-uniform arguments: the common launches (SiLU or
+// no activation, residual none or add, Cout % 4 == 0, one output) run straight-line code compiled for them; all
+// others, and every launch under YDBL_EPI_GENERIC=1, run the form that tests the arguments where they are used.
+// KA: ACT_ANY decides here, in the kernel.  The block-GEMM and spatial-tile kernels, whose accumulators live in
+// AGPRs, are instead compiled per form and chosen on the host (epi_host_form): with both forms in one kernel the
+// register allocator copies the whole accumulator to VGPRs ahead of the dispatch (128x64 igemm 59 -> 70 VGPRs,
+// 5 -> 4 waves per SIMD).  KA = ACT_RT: the runtime form only; a code: that activation, preconditions host-checked.
+constexpr int ACT_ANY = -2;
+template <typename T>
+inline int epi_host_form(const ConvArgs<T>& a) {
+  if (sizeof(T) != 2 || a.epi_generic || (a.Cout & 3) || a.y2 || a.res == YDBL_RES_MUL) return ACT_RT;
+  return a.act == YDBL_ACT_SILU || a.act == YDBL_ACT_NONE ? a.act : ACT_RT;
+}
+template <typename T, int TN, int TM, bool Q8 = false, int KA = ACT_ANY>
+__device__ __forceinline__ void conv_epilogue(const ConvArgs<T>& p, const f32x4 (&acc)[TN][TM],
+                                              const int64_t (&pp)[TM], const bool (&pv)[TM], const int (&co)[TN],
+                                              const float* sb = nullptr, int sb0 = 0) {
+  if constexpr (KA == ACT_RT) {
+    conv_epilogue_as<T, TN, TM, Q8, ACT_RT, -1, false>(p, acc, pp, pv, co, sb, sb0);
+  } else if constexpr (KA != ACT_ANY) {
+    if (p.res == YDBL_RES_ADD) conv_epilogue_as<T, TN, TM, Q8, KA, YDBL_RES_ADD, true>(p, acc, pp, pv, co, sb, sb0);
+    else conv_epilogue_as<T, TN, TM, Q8, KA, YDBL_RES_NONE, true>(p, acc, pp, pv, co, sb, sb0);
+  } else {
+    const bool lean = !std::is_same<T, float>::value && !p.epi_generic && (p.Cout & 3) == 0 && !p.y2 && p.res != YDBL_RES_MUL;
+    if (lean && p.act == YDBL_ACT_SILU) {
+      if (p.res == YDBL_RES_ADD) conv_epilogue_as<T, TN, TM, Q8, YDBL_ACT_SILU, YDBL_RES_ADD, true>(p, acc, pp, pv, co, sb, sb0);
+      else conv_epilogue_as<T, TN, TM, Q8, YDBL_ACT_SILU, YDBL_RES_NONE, true>(p, acc, pp, pv, co, sb, sb0);
+    } else if (lean && p.act == YDBL_ACT_NONE) {
+      if (p.res == YDBL_RES_ADD) conv_epilogue_as<T, TN, TM, Q8, YDBL_ACT_NONE, YDBL_RES_ADD, true>(p, acc, pp, pv, co, sb, sb0);
+      else conv_epilogue_as<T, TN, TM, Q8, YDBL_ACT_NONE, YDBL_RES_NONE, true>(p, acc, pp, pv, co, sb, sb0);
+    } else {
+      conv_epilogue_as<T, TN, TM, Q8, ACT_RT, -1, false>(p, acc, pp, pv, co, sb, sb0);
     }
   }
 }

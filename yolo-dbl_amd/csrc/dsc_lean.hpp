@@ -50,6 +50,9 @@ __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const flo
   static_assert(NTC % TN == 0 && WAVES % NCG == 0, "channel groups over waves");
   constexpr int WPG = WAVES / NCG;
   constexpr int TM = (NTP + WPG - 1) / WPG;          // pixel tiles per wave
+  // the activation / residual forms compiled beside the runtime one (common.hpp, with_act): the 64-channel tiles
+  // only.  On the 512-thread tiles they cost 10-20 VGPRs, and 52 bytes of scratch at 256 input channels.
+  constexpr bool FORMS = C <= 64;
   using L = LeanLds<C, CO, K, S, TH, TW, NT, TAIL>;
   h4* s_x = reinterpret_cast<h4*>(smem + L::X);      // fp16 halo, [row][col][quad]
   f32x4* s_w = reinterpret_cast<f32x4*>(smem + L::W);  // fp32 taps (rounded to fp16), [tap][quad]
@@ -198,10 +201,12 @@ __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const flo
       }
       if (dwb) {  // uniform: DWConv (+ folded BN) bias and activation before the pointwise
         const f32x4 bq = *reinterpret_cast<const f32x4*>(dwb + q * 4);
+        with_act<T>(dw_act, !FORMS || p.epi_generic, [&](auto A) {  // resolved once, not per value (common.hpp)
 #pragma unroll
-        for (int c = 0; c < CSEG; ++c)
+          for (int c = 0; c < CSEG; ++c)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) a[c][e] = apply_act<T>(a[c][e] + bq[e], dw_act);
+            for (int e = 0; e < 4; ++e) a[c][e] = act_as<T, decltype(A)::value>(a[c][e] + bq[e], dw_act);
+        });
       }
       const int ks = q / 8, ql = q % 8;  // k-step and 4-channel slot of this quad
 #pragma unroll
@@ -237,27 +242,43 @@ __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const flo
       for (int q = 0; q < 4; ++q) bv[i][q] = b4[q];
     }
     float ys[TAIL ? TN : 1][TAIL ? TM : 1][4];  // TAIL: the stored y values for the class conv
+    // the epilogue for activation A and residual mode R (codes, or ACT_RT / -1: p.act / p.res at run time)
+    auto epilogue = [&](auto A, auto R) {
+      constexpr int AC = decltype(A)::value, RC = decltype(R)::value;
+      const int res = RC < 0 ? p.res : RC;
 #pragma unroll
-    for (int j = 0; j < TM; ++j) {
-      if (!pv[j]) continue;
+      for (int j = 0; j < TM; ++j) {
+        if (!pv[j]) continue;
 #pragma unroll
-      for (int i = 0; i < TN; ++i) {
-        float v[4];
+        for (int i = 0; i < TN; ++i) {
+          float v[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = apply_act<T>(acc[i][j][q] + bv[i][q], p.act);
-        if (p.res == YDBL_RES_ADD) {
+          for (int q = 0; q < 4; ++q) v[q] = act_as<T, AC>(acc[i][j][q] + bv[i][q], p.act);
+          if (res == YDBL_RES_ADD) {
 #pragma unroll
-          for (int q = 0; q < 4; ++q) v[q] = float(rv[i][j][q]) + v[q];
-        } else if (p.res == YDBL_RES_MUL) {
+            for (int q = 0; q < 4; ++q) v[q] = AC == ACT_RT ? float(rv[i][j][q]) + v[q] : add_rn(float(rv[i][j][q]), v[q]);
+          } else if (res == YDBL_RES_MUL) {
 #pragma unroll
-          for (int q = 0; q < 4; ++q) v[q] = float(rv[i][j][q]) * v[q];
-        }
-        st8(p.y, pp[j] * p.ycs + co[i], v);
-        if constexpr (TAIL) {
+            for (int q = 0; q < 4; ++q) v[q] = float(rv[i][j][q]) * v[q];
+          }
+          st8(p.y, pp[j] * p.ycs + co[i], v);
+          if constexpr (TAIL) {
 #pragma unroll
-          for (int q = 0; q < 4; ++q) ys[i][j][q] = round_to<T>(v[q]);
+            for (int q = 0; q < 4; ++q) ys[i][j][q] = round_to<T>(v[q]);
+          }
         }
       }
+    };
+    // decided once per wave: SiLU / none with residual none / add run straight-line code, the rest the runtime form
+    const bool lean = FORMS && !p.epi_generic && p.res != YDBL_RES_MUL;
+    if (lean && p.act == YDBL_ACT_SILU) {
+      if (p.res == YDBL_RES_ADD) epilogue(ActC<YDBL_ACT_SILU>{}, ActC<YDBL_RES_ADD>{});
+      else epilogue(ActC<YDBL_ACT_SILU>{}, ActC<YDBL_RES_NONE>{});
+    } else if (lean && p.act == YDBL_ACT_NONE) {
+      if (p.res == YDBL_RES_ADD) epilogue(ActC<YDBL_ACT_NONE>{}, ActC<YDBL_RES_ADD>{});
+      else epilogue(ActC<YDBL_ACT_NONE>{}, ActC<YDBL_RES_NONE>{});
+    } else {
+      epilogue(ActC<ACT_RT>{}, ActC<-1>{});
     }
     if constexpr (TAIL && NCG == 1 && TN == 4) {  // Detect class conv over the 64 output channels (CO == 64)
       conv_tail_1x1_vals<T, TN, TM>(p, ys, pp, pv, co, g, reinterpret_cast<const float*>(smem + L::T));

@@ -213,7 +213,9 @@ __global__ __launch_bounds__(256, 2) void dsconv_kernel(ConvArgs<T> p, const flo
   int co[NTN];
 #pragma unroll
   for (int i = 0; i < NTN; ++i) co[i] = co0 + i * 16 + 4 * g;
-  conv_epilogue<T, NTN, TMW>(p, acc, pp, pv, co, s_bias, co0);
+  // the runtime-dispatch form only: a compiled SiLU / none form beside it (conv_common.hpp) cost this kernel 4-24
+  // VGPRs, a wave per SIMD on the k5 / k7 tiles and 20 bytes of scratch on the stride-2 ones
+  conv_epilogue<T, NTN, TMW, false, ACT_RT>(p, acc, pp, pv, co, s_bias, co0);
   if constexpr (NTN == 4) {  // the tail is only launched with Cout 64 = NTN * 16 (host-checked)
     if (p.t3w) conv_tail_1x1<T, NTN, TMW>(p, acc, pp, pv, co, g);
   }
@@ -266,6 +268,7 @@ static ConvArgs<T> ds_args(const ydbl_dsconv_desc* d) {
   a.KW = d->k; a.S = d->stride; a.PAD = d->pad; a.DIL = d->dil;
   a.K = d->x.c; a.KPAD = d->kpad;
   a.act = d->act; a.res = d->res_mode;
+  a.epi_generic = epi_generic();
   if (d->tail_w) {
     a.t3w = d->tail_w; a.t3b = d->tail_b; a.nt3 = d->tail_n;
     a.y3 = reinterpret_cast<T*>(d->tail_y.ptr); a.y3cs = d->tail_y.cs;

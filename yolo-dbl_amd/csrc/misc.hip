@@ -43,14 +43,17 @@ __global__ __launch_bounds__(256) void dwconv_kernel(DView<const T> x, DView<T> 
 #pragma unroll
     for (int q = 0; q < V; ++q) acc[q] += bv[q];
   }
+  float rv[V];
+  if (r.p) load_f<V>(r.at(b, oy, ox) + c0, rv);
+  with_act<T>(act & 0xff, act & ACT_GENERIC, [&](auto A) {  // resolved once, not per value (common.hpp)
+    constexpr int AC = decltype(A)::value;
 #pragma unroll
-  for (int q = 0; q < V; ++q) acc[q] = apply_act<T>(acc[q], act);
-  if (r.p) {
-    float rv[V];
-    load_f<V>(r.at(b, oy, ox) + c0, rv);
+    for (int q = 0; q < V; ++q) acc[q] = act_as<T, AC>(acc[q], act & 0xff);
+    if (r.p) {
 #pragma unroll
-    for (int q = 0; q < V; ++q) acc[q] = rv[q] + acc[q];
-  }
+      for (int q = 0; q < V; ++q) acc[q] = AC == ACT_RT ? rv[q] + acc[q] : add_rn(rv[q], acc[q]);
+    }
+  });
   store_f<V>(y.at(b, oy, ox) + c0, acc);
 }
 
@@ -143,21 +146,24 @@ __global__ __launch_bounds__(256) void dwconv_lds_kernel(DView<const T> x, DView
 #pragma unroll
   for (int q = 0; q < V; ++q) bv[q] = 0.f;
   if (bias) load_f<V>(bias + cc, bv);
+  with_act<T>(act & 0xff, act & ACT_GENERIC, [&](auto A) {  // resolved once, not per value (common.hpp)
+    constexpr int AC = decltype(A)::value;
 #pragma unroll
-  for (int u = 0; u < NPX; ++u) {
-    if (!ok[u]) continue;
-    const int oy = oy0 + py[u], ox = ox0 + px[u];
-    float o[V];
+    for (int u = 0; u < NPX; ++u) {
+      if (!ok[u]) continue;
+      const int oy = oy0 + py[u], ox = ox0 + px[u];
+      float o[V];
 #pragma unroll
-    for (int q = 0; q < V; ++q) o[q] = apply_act<T>(bias ? acc[u][q] + bv[q] : acc[u][q], act);
-    if (r.p) {
-      float rv[V];
-      load_f<V>(r.at(b, oy, ox) + cc, rv);
+      for (int q = 0; q < V; ++q) o[q] = act_as<T, AC>(bias ? acc[u][q] + bv[q] : acc[u][q], act & 0xff);
+      if (r.p) {
+        float rv[V];
+        load_f<V>(r.at(b, oy, ox) + cc, rv);
 #pragma unroll
-      for (int q = 0; q < V; ++q) o[q] = rv[q] + o[q];
+        for (int q = 0; q < V; ++q) o[q] = AC == ACT_RT ? rv[q] + o[q] : add_rn(rv[q], o[q]);
+      }
+      store_f<V>(y.at(b, oy, ox) + cc, o);
     }
-    store_f<V>(y.at(b, oy, ox) + cc, o);
-  }
+  });
 }
 
 template <typename T>
@@ -168,7 +174,7 @@ static bool launch_dw_lds(const ydbl_dwconv_desc* d, DView<const T> x, DView<T> 
     if (d->y.c % (cv * V)) return false;
     const int tiles_x = (int)cdiv(d->y.w, tw), tiles_y = (int)cdiv(d->y.h, th);
     const int64_t blocks = (int64_t)d->y.n * tiles_y * tiles_x * (d->y.c / (cv * V));
-    kern<<<(unsigned)blocks, 256, 0, s>>>(x, y, r, d->w, d->bias, d->pad, d->act, tiles_x, tiles_y);
+    kern<<<(unsigned)blocks, 256, 0, s>>>(x, y, r, d->w, d->bias, d->pad, epi_act(d->act), tiles_x, tiles_y);
     return true;
   };
   // f16: 8 vectors = 64 channels per workgroup; f32: 8 vectors = 32 channels
@@ -226,8 +232,10 @@ __device__ __forceinline__ void dw_pair_phase(const typename Vec<T>::type* src, 
       }
     }
     float o[V];
+    with_act<T>(act & 0xff, act & ACT_GENERIC, [&](auto A) {  // resolved once per pixel, not per value (common.hpp)
 #pragma unroll
-    for (int q = 0; q < V; ++q) o[q] = apply_act<T>(bias ? acc[q] + bv[q] : acc[q], act);
+      for (int q = 0; q < V; ++q) o[q] = act_as<T, decltype(A)::value>(bias ? acc[q] + bv[q] : acc[q], act & 0xff);
+    });
     store_f<V>(out.at(b, oy, ox) + cc, o);
     if (keep) {
       vec t;
@@ -553,11 +561,11 @@ extern "C" int ydbl_dwconv2d_nhwc(const ydbl_dwconv_desc* d, void* stream) {
   if (d->x.dtype == YDBL_F16)
     dwconv_kernel<_Float16><<<nblk(total), 256, 0, s>>>(cview<_Float16>(&d->x), dview<_Float16>(d->y),
                                                         cview<_Float16>(res ? &d->r : nullptr), d->w, d->bias,
-                                                        d->kh, d->kw, d->stride, d->pad, d->dil, d->act);
+                                                        d->kh, d->kw, d->stride, d->pad, d->dil, epi_act(d->act));
   else
     dwconv_kernel<float><<<nblk(total), 256, 0, s>>>(cview<float>(&d->x), dview<float>(d->y),
                                                      cview<float>(res ? &d->r : nullptr), d->w, d->bias, d->kh, d->kw,
-                                                     d->stride, d->pad, d->dil, d->act);
+                                                     d->stride, d->pad, d->dil, epi_act(d->act));
   return check_launch("ydbl_dwconv2d_nhwc");
 }
 
@@ -585,11 +593,11 @@ extern "C" int ydbl_dwconv2d_pair_nhwc(const ydbl_dwconv_desc* d0, const ydbl_dw
   if (d0->x.dtype == YDBL_F16)
     dw_pair_kernel<_Float16, 5, 1, 7, 3, CV, NT><<<blocks, NT, 0, s>>>(
         cview<_Float16>(&d0->x), dview<_Float16>(d0->y), dview<_Float16>(d1->y), d0->w, d0->bias, d1->w, d1->bias,
-        d0->pad, d1->pad, d0->act, d1->act);
+        d0->pad, d1->pad, epi_act(d0->act), epi_act(d1->act));
   else
     dw_pair_kernel<float, 5, 1, 7, 3, CV, NT><<<blocks, NT, 0, s>>>(
         cview<float>(&d0->x), dview<float>(d0->y), dview<float>(d1->y), d0->w, d0->bias, d1->w, d1->bias, d0->pad,
-        d1->pad, d0->act, d1->act);
+        d1->pad, epi_act(d0->act), epi_act(d1->act));
   return check_launch("ydbl_dwconv2d_pair_nhwc");
 }
 
