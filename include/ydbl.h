@@ -46,6 +46,9 @@
  *   ydbl_detect_decode     <- Detect._inference head.py:143-181 + DFL block.py:79-83 +
  *                             make_anchors/dist2bbox utils/tal.py:333-357 + NMS candidate
  *                             filter utils/ops.py:234-276
+ *   ydbl_detect_decode_aug <- the same for one pass of DetectionModel._predict_augment nn/tasks.py:361-398
+ *                             (_descale_pred, _clip_augmented and the concatenation done as it writes)
+ *   ydbl_scale_img         <- scale_img utils/torch_utils.py:423-432 (+ x.flip(3), nn/tasks.py:371)
  *   ydbl_pred_candidates   <- utils/ops.py:234-276 on a [B,4+nc,A] prediction tensor
  *   ydbl_nms               <- utils/ops.py:278-310 (+ torchvision.ops.nms, torchvision 0.23.0),
  *                             with clip_boxes utils/ops.py:319-338 as reached through
@@ -300,6 +303,33 @@ typedef struct {
 } ydbl_decode_desc;
 int ydbl_detect_decode(const ydbl_decode_desc* d, void* stream);
 
+/* One pass of test-time augmentation (DetectionModel._predict_augment, nn/tasks.py:361-398): ydbl_detect_decode of
+ * a pass's head maps with the reference's _descale_pred and _clip_augmented applied as the values are written, so
+ * that the three passes fill ONE prediction tensor y[n][4+nc][y_stride] and ONE candidate list, which a single
+ * ydbl_nms then reads.  d is the pass's plain decode descriptor; the record below adds:
+ *   scale     xywh are divided by it (IEEE fp32 division: torch's p[:, :4] /= scale; a reciprocal multiply differs
+ *             on ~20 % of values); 0 = 1 = no de-scale
+ *   flip_w    != 0: cx = flip_w - cx after the division (the left-right de-flip; flip_w = the input width)
+ *   a_lo,a_hi the window [a_lo, a_hi) of the pass's own anchor order that survives _clip_augmented; anchors outside
+ *             it are neither written to y_ref nor offered as candidates (a_hi = 0: every anchor)
+ *   pos_base  position of anchor a_lo on the merged anchor axis: anchor a lands at pos = pos_base + (a - a_lo),
+ *             y_ref column pos, and carries cand_idx = pos (pos * nc + cls when multi_label) -- ydbl_nms's
+ *             (score desc, idx asc) order is then the reference's stable sort over the concatenation
+ *   y_stride  row stride of y_ref in floats = the merged anchor count (0: the pass's own anchor count)
+ *   append    nonzero: cand_count is NOT zeroed by this call (the first pass zeroes it, the later ones add);
+ *             d->cap is the capacity of the shared list (the merged anchor count, x nc when multi_label)
+ * The candidate boxes are xywh2xyxy of the de-scaled, de-flipped xywh, as the reference's NMS computes them from the
+ * merged tensor.  An all-zero record is ydbl_detect_decode exactly. */
+typedef struct {
+  float scale;
+  float flip_w;
+  int32_t a_lo, a_hi;
+  int32_t pos_base;
+  int32_t y_stride;
+  int32_t append;
+} ydbl_decode_aug;
+int ydbl_detect_decode_aug(const ydbl_decode_desc* d, const ydbl_decode_aug* g, void* stream);
+
 /* NMS candidates straight from a prediction tensor in the reference layout
  * pred fp32 [n][4+nc][A] (xywh pixels, class scores), as U/utils/ops.py:234-276 reads it.
  * Same candidate outputs / semantics as ydbl_detect_decode. */
@@ -405,6 +435,22 @@ typedef struct {
   float* out;
 } ydbl_letterbox_desc;
 int ydbl_letterbox(const ydbl_letterbox_desc* d, void* stream);
+
+/* scale_img of test-time augmentation (utils/torch_utils.py:423-432) with the source's left-right flip folded in:
+ * y[:, :, :sh, :sw] = bilinear resize (F.interpolate align_corners=False, no antialias; torch's fp32 source-index
+ * rule, see scale_img.hip) of x (flip: of x.flip(3)) to (sh, sw); the rest of y [n][c][hp][wp] = pad_value (the
+ * reference pads right and bottom with 0.447).  x fp32 [n][c][h][w], both dense; sh <= hp, sw <= wp.  The resize
+ * ratio is implied by (sh, sw): the caller computes sh = int(h * ratio), hp = ceil(h * ratio / gs) * gs. */
+typedef struct {
+  const float* x;
+  int32_t n, c, h, w;
+  int32_t sh, sw;    /* resized extent */
+  int32_t hp, wp;    /* padded output extent */
+  int32_t flip;      /* nonzero: read the source mirrored left-right */
+  float pad_value;
+  float* y;
+} ydbl_scale_img_desc;
+int ydbl_scale_img(const ydbl_scale_img_desc* d, void* stream);
 
 /* mAP true-positive matrix of a batch of NMS outputs against ground-truth labels.
  * det fp32 [n][max_det][6] (x1,y1,x2,y2,conf,cls) + det_count int32 [n] (ydbl_nms outputs);

@@ -5,6 +5,8 @@
 //          a per-image atomic counter; candidate order is irrelevant because NMS sorts by
 //          (score desc, original index asc), which is exactly the order torchvision's stable sort
 //          gives the reference (anchor order, or torch.where's (anchor, class) row-major order).
+//          decode_aug (test-time augmentation, U/nn/tasks.py:361-398): the same per pass, with the pass's de-scale,
+//          de-flip, anchor window and position on the merged anchor axis; three passes fill one candidate list.
 // nms    : images with <= 8192 candidates: chip-wide ranks (= the stable sort's positions) and rank-space
 //          IoU > thr bit rows, then one 1024-thread workgroup per image sweeps 64-rank blocks (the pair-matrix
 //          path below); larger images: a per-image radix select of the first max_nms sort keys, sorted in
@@ -64,12 +66,24 @@ __device__ __forceinline__ bool class_ok(int j, const int* classes, int ncls) {
 // instead of 64, and the launch has four times the waves to hide it.  Same arithmetic per value as one lane per
 // anchor: the decoded boxes, scores and candidate sets are unchanged (candidate order within an image may differ;
 // every candidate carries its anchor / class index).
-template <typename T>
-__global__ __launch_bounds__(256) void decode_kernel(DecodeArgs<T> p) {
+//
+// AUG: one pass of test-time augmentation (include/ydbl.h ydbl_decode_aug).  Anchors outside the pass's window
+// leave at once (whole quads); the others de-scale and de-flip xywh, and land at their position of the merged
+// anchor axis -- y_ref column, row stride and candidate index.  Without AUG none of it is compiled in.
+struct AugArgs {
+  float scale, flip_w;
+  int a_lo, a_hi, pos_base, ystride;
+};
+
+template <typename T, bool AUG>
+__device__ __forceinline__ void decode_body(const DecodeArgs<T>& p, const AugArgs& g) {
   const int b = blockIdx.y;
   const int tq = blockIdx.x * blockDim.x + threadIdx.x;
   const int a = tq >> 2, s = tq & 3;
   if (a >= p.A) return;  // whole quads
+  if constexpr (AUG) {
+    if (a < g.a_lo || a >= g.a_hi) return;
+  }
   int l = 0;
   while (l < p.nl - 1 && a >= p.a_end[l]) ++l;
   const int a0 = l ? p.a_end[l - 1] : 0;
@@ -105,11 +119,19 @@ __global__ __launch_bounds__(256) void decode_kernel(DecodeArgs<T> p) {
   for (int k = 0; k < 4; ++k) dist[k] = __shfl(mine, q0 + k);
   const float ax = float(gx) + 0.5f, ay = float(gy) + 0.5f, st = p.stride[l];
   const float x1 = ax - dist[0], y1 = ay - dist[1], x2 = ax + dist[2], y2 = ay + dist[3];
-  const float cx = ((x1 + x2) / 2.0f) * st, cy = ((y1 + y2) / 2.0f) * st;
-  const float w = (x2 - x1) * st, h = (y2 - y1) * st;
-  const int64_t A = p.A;
+  float cx = ((x1 + x2) / 2.0f) * st, cy = ((y1 + y2) / 2.0f) * st;
+  float w = (x2 - x1) * st, h = (y2 - y1) * st;
+  int64_t A = p.A;
+  int pos = a;  // the anchor's column of y_ref and its candidate index
+  if constexpr (AUG) {
+    // _descale_pred (U/nn/tasks.py:378-387): p[:, :4] /= scale, an IEEE division, then x = img_w - x
+    cx = __fdiv_rn(cx, g.scale); cy = __fdiv_rn(cy, g.scale); w = __fdiv_rn(w, g.scale); h = __fdiv_rn(h, g.scale);
+    if (g.flip_w != 0.f) cx = g.flip_w - cx;
+    A = g.ystride;
+    pos = g.pos_base + (a - g.a_lo);
+  }
   if (p.yref) {
-    float* yr = p.yref + (int64_t)b * (4 + p.nc) * A + a;
+    float* yr = p.yref + (int64_t)b * (4 + p.nc) * A + pos;
     yr[s * A] = s == 0 ? cx : s == 1 ? cy : s == 2 ? w : h;
   }
   // xywh2xyxy (U/utils/ops.py:416-433)
@@ -120,14 +142,14 @@ __global__ __launch_bounds__(256) void decode_kernel(DecodeArgs<T> p) {
   int bj = 0;
   for (int j = s; j < p.nc; j += 4) {
     const float sc = 1.0f / (1.0f + expf(-float(cp[j])));
-    if (p.yref) p.yref[((int64_t)b * (4 + p.nc) + 4 + j) * A + a] = sc;
+    if (p.yref) p.yref[((int64_t)b * (4 + p.nc) + 4 + j) * A + pos] = sc;
     if (p.multi) {
       const int slot = wave_slot(p.ccount + b, sc > p.conf && class_ok(j, p.classes, p.ncls));
       if (slot >= 0) {
         if (slot < p.cap) {
           const int64_t o = (int64_t)b * p.cap + slot;
           *reinterpret_cast<f32x4*>(p.cbox + o * 4) = f32x4{bx1, by1, bx2, by2};
-          p.cscore[o] = sc; p.ccls[o] = j; p.cidx[o] = a * p.nc + j;
+          p.cscore[o] = sc; p.ccls[o] = j; p.cidx[o] = pos * p.nc + j;
         }
       }
     } else if (sc > best) {  // torch.max: first index of the maximum (within this lane's classes)
@@ -151,9 +173,18 @@ __global__ __launch_bounds__(256) void decode_kernel(DecodeArgs<T> p) {
     if (slot < p.cap) {
       const int64_t o = (int64_t)b * p.cap + slot;
       *reinterpret_cast<f32x4*>(p.cbox + o * 4) = f32x4{bx1, by1, bx2, by2};
-      p.cscore[o] = best; p.ccls[o] = bj; p.cidx[o] = a;
+      p.cscore[o] = best; p.ccls[o] = bj; p.cidx[o] = pos;
     }
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void decode_kernel(DecodeArgs<T> p) {
+  decode_body<T, false>(p, AugArgs{});
+}
+template <typename T>
+__global__ __launch_bounds__(256) void decode_aug_kernel(DecodeArgs<T> p, AugArgs g) {
+  decode_body<T, true>(p, g);
 }
 
 // Candidates from a prediction tensor in the reference layout pred[b][4+nc][A] (xywh, scores).
@@ -1234,7 +1265,7 @@ static DView<const T> cvw(const ydbl_view& v) {
 }
 
 template <typename T>
-static int decode_t(const ydbl_decode_desc* d, hipStream_t s) {
+static int decode_t(const ydbl_decode_desc* d, const ydbl_decode_aug* g, hipStream_t s) {
   DecodeArgs<T> a{};
   int A = 0;
   for (int l = 0; l < d->nl; ++l) {
@@ -1251,16 +1282,32 @@ static int decode_t(const ydbl_decode_desc* d, hipStream_t s) {
   a.cbox = d->cand_box; a.cscore = d->cand_score; a.ccls = d->cand_cls; a.cidx = d->cand_idx; a.ccount = d->cand_count;
   a.cap = d->cap;
   const int B = d->box[0].n;
-  zero_counts_kernel<<<1, 256, 0, s>>>(d->cand_count, B);
-  decode_kernel<T><<<dim3((unsigned)cdiv((int64_t)A * 4, 256), B), 256, 0, s>>>(a);  // a quad per anchor
-  return check_launch("ydbl_detect_decode");
+  const dim3 grid((unsigned)cdiv((int64_t)A * 4, 256), B);  // a quad per anchor
+  if (!g) {
+    zero_counts_kernel<<<1, 256, 0, s>>>(d->cand_count, B);
+    decode_kernel<T><<<grid, 256, 0, s>>>(a);
+    return check_launch("ydbl_detect_decode");
+  }
+  AugArgs ga;
+  ga.scale = g->scale == 0.f ? 1.f : g->scale;
+  ga.flip_w = g->flip_w;
+  ga.a_lo = g->a_lo;
+  ga.a_hi = g->a_hi ? g->a_hi : A;
+  ga.pos_base = g->pos_base;
+  ga.ystride = g->y_stride ? g->y_stride : A;
+  if (ga.a_hi > A || ga.a_lo >= ga.a_hi) return fail(YDBL_EINVAL, "decode_aug: anchor window outside the pass");
+  if (ga.ystride < ga.pos_base + (ga.a_hi - ga.a_lo))
+    return fail(YDBL_EINVAL, "decode_aug: y_stride below pos_base + the window");
+  if (!g->append) zero_counts_kernel<<<1, 256, 0, s>>>(d->cand_count, B);
+  decode_aug_kernel<T><<<grid, 256, 0, s>>>(a, ga);
+  return check_launch("ydbl_detect_decode_aug");
 }
 
 }  // namespace ydbl
 
 using namespace ydbl;
 
-extern "C" int ydbl_detect_decode(const ydbl_decode_desc* d, void* stream) {
+static int decode_entry(const ydbl_decode_desc* d, const ydbl_decode_aug* g, void* stream) {
   if (!d) return fail(YDBL_EINVAL, "decode: null descriptor");
   if (d->nl < 1 || d->nl > 3) return fail(YDBL_EINVAL, "decode: 1..3 levels");
   for (int l = 0; l < d->nl; ++l) {
@@ -1275,7 +1322,18 @@ extern "C" int ydbl_detect_decode(const ydbl_decode_desc* d, void* stream) {
   if (!d->cand_box || !d->cand_score || !d->cand_cls || !d->cand_idx || !d->cand_count || d->cap < 1)
     return fail(YDBL_EINVAL, "decode: null candidate buffers");
   hipStream_t s = as_stream(stream);
-  return d->box[0].dtype == YDBL_F16 ? decode_t<_Float16>(d, s) : decode_t<float>(d, s);
+  return d->box[0].dtype == YDBL_F16 ? decode_t<_Float16>(d, g, s) : decode_t<float>(d, g, s);
+}
+
+extern "C" int ydbl_detect_decode(const ydbl_decode_desc* d, void* stream) { return decode_entry(d, nullptr, stream); }
+
+extern "C" int ydbl_detect_decode_aug(const ydbl_decode_desc* d, const ydbl_decode_aug* g, void* stream) {
+  if (!g) return fail(YDBL_EINVAL, "decode_aug: null augmentation record");
+  if (!(g->scale >= 0.f) || !std::isfinite(g->scale) || !std::isfinite(g->flip_w))
+    return fail(YDBL_EINVAL, "decode_aug: scale must be finite and >= 0 (0 = none), flip_w finite");
+  if (g->a_lo < 0 || g->a_hi < 0 || g->pos_base < 0 || g->y_stride < 0)
+    return fail(YDBL_EINVAL, "decode_aug: negative window, position or stride");
+  return decode_entry(d, g, stream);
 }
 
 extern "C" int ydbl_pred_candidates(const ydbl_pred_cand_desc* d, void* stream) {

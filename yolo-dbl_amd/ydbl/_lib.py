@@ -64,6 +64,18 @@ class DecodeDesc(C.Structure):
                 ("cand_idx", C.c_void_p), ("cand_count", C.c_void_p), ("cap", C.c_int32)]
 
 
+class DecodeAug(C.Structure):
+    """ydbl_decode_aug: one test-time-augmentation pass's de-scale / de-flip / anchor window / merged position."""
+    _fields_ = [("scale", C.c_float), ("flip_w", C.c_float), ("a_lo", C.c_int32), ("a_hi", C.c_int32),
+                ("pos_base", C.c_int32), ("y_stride", C.c_int32), ("append", C.c_int32)]
+
+
+class ScaleImgDesc(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("n", C.c_int32), ("c", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("sh", C.c_int32), ("sw", C.c_int32), ("hp", C.c_int32), ("wp", C.c_int32), ("flip", C.c_int32),
+                ("pad_value", C.c_float), ("y", C.c_void_p)]
+
+
 class PredCandDesc(C.Structure):
     _fields_ = [("pred", C.c_void_p), ("n", C.c_int32), ("nc", C.c_int32), ("A", C.c_int32),
                 ("conf_thres", C.c_float), ("multi_label", C.c_int32), ("classes", C.c_void_p),
@@ -154,6 +166,8 @@ SIGNATURES = {
     "ydbl_hg_fused": ([C.POINTER(HgDesc), _P], C.c_int),
     "ydbl_dysample2": ([C.POINTER(DySample2Desc), _P], C.c_int),
     "ydbl_detect_decode": ([C.POINTER(DecodeDesc), _P], C.c_int),
+    "ydbl_detect_decode_aug": ([C.POINTER(DecodeDesc), C.POINTER(DecodeAug), _P], C.c_int),
+    "ydbl_scale_img": ([C.POINTER(ScaleImgDesc), _P], C.c_int),
     "ydbl_pred_candidates": ([C.POINTER(PredCandDesc), _P], C.c_int),
     "ydbl_nms_workspace": ([C.c_int32, C.c_int32, C.c_int32], C.c_int64),
     "ydbl_conv_workspace": ([C.POINTER(ConvDesc)], C.c_int64),

@@ -21,14 +21,27 @@ import torch
 
 from ..nn.tasks import DetectionModel, weights_signature, ydbl_env
 from .results import Results
-from .session import DetectSession, default_streams
+from .session import AugmentSession, DetectSession, default_streams
 
 DEFAULTS = {"conf": 0.25, "iou": 0.7, "max_det": 300, "half": False, "fp8": False, "device": None, "agnostic_nms": False,
             "classes": None, "batch": 1, "verbose": False, "imgsz": 640,
             # sub-batch graphs per session (DetectSession): None = default_streams(batch), the benched layout
             "streams": None,
             # fp8: an ydbl.quant.Fp8Calibration or its JSON file (None: calibrate on the first batch)
-            "fp8_calibration": None}
+            "fp8_calibration": None,
+            # test-time augmentation (U/nn/tasks.py:361-398): three passes (1, 0.83 flipped, 0.67), one NMS
+            "augment": False}
+
+
+def check_augment(augment, fp8=False, gather_rows=None) -> bool:
+    """augment's scope guards, before any device work: no fp8 (its calibration is per compiled plan; the augmented
+    session runs three) and no record rows of the batch-sharded predictor."""
+    if augment and fp8:
+        raise NotImplementedError("augment=True with fp8 is not implemented: the fp8 calibration is per compiled "
+                                  "plan and the augmented session runs three; use half=True")
+    if augment and gather_rows is not None:
+        raise NotImplementedError("augment=True is not implemented for the batch-sharded predictor (gather_rows)")
+    return bool(augment)
 
 
 def select_device(device=None) -> torch.device:
@@ -221,10 +234,12 @@ class Model:
 
     def session(self, batch, h, w, half=False, conf=0.25, iou=0.7, max_det=300, agnostic=False, classes=None,
                 multi_label=False, device=None, keep_pred=False, use_graph=True, fp8=False, clip=True,
-                streams=1, gather_rows=None, nms=True, fp8_calibration=None) -> DetectSession:
+                streams=1, gather_rows=None, nms=True, fp8_calibration=None, augment=False) -> DetectSession:
         """A compiled (batch, h, w, dtype, NMS settings) inference session; streams > 1 splits the batch into
         that many concurrently replayed sub-batch graphs (DetectSession); streams=None: default_streams(batch),
-        the layout predict() runs and bench.py times."""
+        the layout predict() runs and bench.py times.  augment=True: the test-time-augmentation session
+        (AugmentSession: three passes, one NMS over their union; no fp8)."""
+        augment = check_augment(augment, fp8, gather_rows)
         if streams is None:
             streams = default_streams(batch)
         dev = select_device(device)
@@ -232,7 +247,7 @@ class Model:
         key = (batch, h, w, dtype, float(conf), float(iou), int(max_det), bool(agnostic),
                tuple(classes) if classes is not None else None, bool(multi_label), str(dev), keep_pred, use_graph,
                float(fp8), bool(clip), int(streams), gather_rows, bool(nms),
-               _calib_key(fp8_calibration),
+               _calib_key(fp8_calibration), augment,
                # the remaining YDBL_* switches (plan-builder fusions in ydbl.nn.modules; YDBL_DS_LEAN / YDBL_NMS_*
                # in the C-ABI) are read at plan build or at each launch, so a captured graph keeps the routing of
                # its capture: a different switch setting is a different session
@@ -242,9 +257,15 @@ class Model:
             while len(self._sessions) >= self.MAX_SESSIONS:
                 self._sessions.popitem(last=False)  # least recently used; its buffers go with the last reference
             with torch.cuda.device(dev):
-                s = DetectSession(self.model, batch, h, w, dtype, conf, iou, max_det, multi_label, agnostic, classes,
-                                  keep_pred=keep_pred, use_graph=use_graph, device=dev, fp8=fp8, clip=clip,
-                                  streams=streams, gather_rows=gather_rows, nms=nms, fp8_calibration=fp8_calibration)
+                if augment:
+                    s = AugmentSession(self.model, batch, h, w, dtype, conf, iou, max_det, multi_label, agnostic,
+                                       classes, keep_pred=keep_pred, use_graph=use_graph, device=dev, clip=clip,
+                                       streams=streams, nms=nms)
+                else:
+                    s = DetectSession(self.model, batch, h, w, dtype, conf, iou, max_det, multi_label, agnostic,
+                                      classes, keep_pred=keep_pred, use_graph=use_graph, device=dev, fp8=fp8,
+                                      clip=clip, streams=streams, gather_rows=gather_rows, nms=nms,
+                                      fp8_calibration=fp8_calibration)
             s.wsig = weights_signature(self.model)  # the weights its plans folded (see _stale)
             self._sessions[key] = s
         else:
@@ -276,11 +297,13 @@ class Model:
           - str / Path: an image file, a directory, a glob or a *.txt list (LoadImagesAndVideos): batches of
             ``batch`` images (default 1) in sorted file order.
         Non-tensor sources are letterboxed to imgsz on the GPU and their boxes come back in the original
-        image's coordinates.
+        image's coordinates.  augment=True: the reference's test-time augmentation (U/nn/tasks.py:361-398) for every
+        source kind -- the (letterboxed) batch also runs at 0.83x mirrored and at 0.67x, one NMS over all three.
         """
         from .sources import check_path_source, file_batches, frames_from_images, is_frame_source
 
         args = {**DEFAULTS, **self.overrides, **kwargs}
+        check_augment(args["augment"], args["fp8"])
         dev = select_device(args["device"])
         t0 = time.perf_counter()
         if source is None:
@@ -301,7 +324,7 @@ class Model:
         b, _, h, w = im.shape
         kw = dict(half=args["half"], conf=args["conf"], iou=args["iou"], max_det=args["max_det"],
                   agnostic=args["agnostic_nms"], classes=args["classes"], device=dev, fp8=args["fp8"],
-                  streams=args["streams"], fp8_calibration=args["fp8_calibration"])
+                  streams=args["streams"], fp8_calibration=args["fp8_calibration"], augment=args["augment"])
         s = self.session(b, h, w, **kw)
         t1 = time.perf_counter()
         one, inv = _scale_consts(dev)
@@ -356,14 +379,15 @@ class Model:
         # the reference's NMS does not clip: boxes are clipped to the frame by scale_boxes
         s = self.session(b, h, w, half=args["half"], conf=args["conf"], iou=args["iou"], max_det=args["max_det"],
                          agnostic=args["agnostic_nms"], classes=args["classes"], device=dev, fp8=args["fp8"],
-                         clip=False, streams=args["streams"], fp8_calibration=args["fp8_calibration"])
+                         clip=False, streams=args["streams"], fp8_calibration=args["fp8_calibration"],
+                         augment=args["augment"])
         t1 = time.perf_counter()
         det, cnt = s(im)
         if self._stale(s):
             det, cnt = self.session(b, h, w, half=args["half"], conf=args["conf"], iou=args["iou"],
                                     max_det=args["max_det"], agnostic=args["agnostic_nms"], classes=args["classes"],
                                     device=dev, fp8=args["fp8"], clip=False, streams=args["streams"],
-                                    fp8_calibration=args["fp8_calibration"])(im)
+                                    fp8_calibration=args["fp8_calibration"], augment=args["augment"])(im)
         counts = cnt.tolist()
         t2 = time.perf_counter()
         results = []
@@ -383,11 +407,14 @@ class Model:
 
     def val(self, data=None, **kwargs):
         """Detection mAP (U/engine/model.py:609-643): ``data`` = a data YAML, a dataset folder, an image folder /
-        list, or in-memory batches; see ydbl.engine.validator.  rect batches by default, like the reference."""
+        list, or in-memory batches; see ydbl.engine.validator.  rect batches by default, like the reference.
+        augment=True validates the test-time-augmented predictions (U/engine/validator.py: model(img, augment=...))."""
         from .validator import DetectionValidator
 
         args = {**DEFAULTS, "conf": 0.001, "iou": 0.7, "batch": 16, "rect": True, "split": "val", **kwargs}
-        return DetectionValidator(self, args)(data)
+        check_augment(args["augment"], args["fp8"])
+        self.validator = DetectionValidator(self, args)  # kept: its per-image stats (tp, conf, pred_cls, target_cls)
+        return self.validator(data)
 
 
 class YOLO(Model):

@@ -12,6 +12,7 @@ boxes back with scale_boxes (U/utils/ops.py:92-127), done here with device tenso
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -101,6 +102,43 @@ def letterbox_frames(frames, meta, out_h, out_w, device="cuda", pad=114.0, out=N
     _lib.check(_lib.lib.ydbl_letterbox(C.byref(d), stream), "ydbl_letterbox")
     # keep the staging buffers alive until the kernel has read them
     torch.cuda.current_stream(dev).synchronize()
+    return out
+
+
+SCALE_IMG_PAD = 0.447  # the reference's pad value (imagenet mean, U/utils/torch_utils.py:432)
+
+
+def scale_img_shape(h: int, w: int, ratio: float, gs: int = 32):
+    """scale_img's sizes (U/utils/torch_utils.py:427-431): the resized extent (int(h * ratio), int(w * ratio)) and
+    the padded one, ceil(h * ratio / gs) * gs per axis -- the ceil of the product, not of the truncated size."""
+    return (int(h * ratio), int(w * ratio)), tuple(math.ceil(v * ratio / gs) * gs for v in (h, w))
+
+
+def scale_img(x: torch.Tensor, ratio: float = 1.0, flip: bool = False, gs: int = 32,
+              out: torch.Tensor | None = None) -> torch.Tensor:
+    """``scale_img(x.flip(3) if flip else x, ratio, gs=gs)`` of the reference (U/utils/torch_utils.py:423-432, as
+    test-time augmentation calls it, U/nn/tasks.py:371) on the GPU, one ydbl_scale_img launch: bilinear resize
+    (align_corners=False) to (int(h * ratio), int(w * ratio)), padded right and bottom with 0.447 to multiples of gs.
+    x: fp32 BCHW device tensor; returns a new device tensor (or fills ``out``).  ratio 1.0 returns the (flipped)
+    input as it is, like the reference."""
+    if not isinstance(x, torch.Tensor) or x.ndim != 4:
+        raise TypeError("scale_img takes a BCHW tensor")
+    if x.device.type != "cuda":
+        raise RuntimeError(f"scale_img runs on the GPU (ydbl_scale_img); got a tensor on {x.device}")
+    if x.dtype != torch.float32:
+        raise TypeError(f"scale_img takes float32, got {x.dtype}")
+    if ratio == 1.0:
+        return x.flip(3) if flip else x
+    x = x.contiguous()
+    b, c, h, w = x.shape
+    (sh, sw), (hp, wp) = scale_img_shape(h, w, ratio, gs)
+    if out is None:
+        out = torch.empty((b, c, hp, wp), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (b, c, hp, wp) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous fp32 {(b, c, hp, wp)}")
+    d = _lib.ScaleImgDesc(x.data_ptr(), b, c, h, w, sh, sw, hp, wp, int(bool(flip)), SCALE_IMG_PAD, out.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.check(_lib.lib.ydbl_scale_img(C.byref(d), stream), "ydbl_scale_img")
     return out
 
 

@@ -15,7 +15,7 @@ import weakref
 import torch
 
 from .. import _lib
-from .._lib import DecodeDesc, NmsDesc, View
+from .._lib import DecodeAug, DecodeDesc, NmsDesc, ScaleImgDesc, View
 from ..runtime import BranchGraphRunner, GraphRunner, Plan
 
 
@@ -416,3 +416,144 @@ class DetectSession:
             per = [c.compiled.feats() for c in self.children]
             return [torch.cat([f[i] for f in per]) for i in range(len(per[0]))]
         return self.compiled.feats()
+
+
+# Test-time augmentation (DetectionModel._predict_augment, U/nn/tasks.py:361-376): (ratio, left-right flip) per pass
+AUG_PASSES = ((1.0, False), (0.83, True), (0.67, False))
+
+
+def augment_passes(h: int, w: int, strides) -> list:
+    """The three passes of augmented inference on an (h, w) input, as pure host arithmetic: per pass
+    ``(ratio, flip, (sh, sw), (hp, wp), A, a_lo, a_hi, pos_base)`` -- scale_img's resized and padded sizes
+    (preprocess.scale_img_shape, gs = the largest stride), the pass's anchor count A over ``strides``, the window
+    [a_lo, a_hi) of its anchors that _clip_augmented keeps (U/nn/tasks.py:389-398: with g = sum(4**k, k < nl) the
+    first pass loses its last A // g anchors -- its coarsest level at a square-ish size --, the last pass its first
+    (A // g) * 4**(nl - 1) -- its finest), and the position of a_lo on the concatenated anchor axis."""
+    from .preprocess import scale_img_shape
+
+    strides = [int(s) for s in strides]
+    nl, gs = len(strides), max(strides)
+    g = sum(4 ** k for k in range(nl))
+    out, pos = [], 0
+    for i, (ratio, flip) in enumerate(AUG_PASSES):
+        (sh, sw), (hp, wp) = ((h, w), (h, w)) if ratio == 1.0 else scale_img_shape(h, w, ratio, gs)
+        A = sum((hp // s) * (wp // s) for s in strides)
+        a_lo, a_hi = 0, A
+        if i == 0:
+            a_hi = A - A // g
+        if i == len(AUG_PASSES) - 1:
+            a_lo = (A // g) * 4 ** (nl - 1)
+        out.append((ratio, flip, (sh, sw), (hp, wp), A, a_lo, a_hi, pos))
+        pos += a_hi - a_lo
+    return out
+
+
+class AugmentSession(DetectSession):
+    """``augment=True``: the reference's multi-scale + flip test-time augmentation as one launch plan.  Three compiled
+    forwards at the shapes of augment_passes() share one candidate list, one det | count output and (keep_pred) one
+    merged ``pred [B, 4+nc, A_tot]``:
+
+        load() -> pass 0's staging buffer (LoadTensor-scaled, the copy path)
+        ydbl_scale_img x 2            pass 0's staging buffer -> the staging buffers of passes 1 and 2
+        per pass: forward, ydbl_detect_decode_aug   (de-scale, de-flip, anchor window, merged position; pass 0
+                                                     zeroes the candidate counters, passes 1 and 2 append)
+        ydbl_nms                      once, over the union, clipping to the original (h, w)
+
+    all on one stream, captured as one hipGraph (use_graph): no host round trip between the passes.  streams = k
+    splits the batch as DetectSession does, each sub-batch running its own three passes as one branch of the graph.
+    There is no in-place input binding (can_bind() is False: predict() takes the copy path) and no fp8 (the
+    calibration is per plan).  The NMS candidate capacity is A_tot (x nc multi-label): 15 049 at 640^2, above
+    ydbl_nms's 8192-candidate pair-matrix limit like the plain session's 8400, so its workspace per image is the
+    same ~9.1 MB (ydbl_nms_workspace: 16384 sort slots, 8 class-group lists, 8192 pair-matrix rows)."""
+
+    def __init__(self, model, batch: int, h: int, w: int, dtype=torch.float16, conf=0.25, iou=0.7, max_det=300,
+                 multi_label=False, agnostic=False, classes=None, max_nms=30000, max_wh=7680, clip=True,
+                 keep_pred=False, use_graph=True, device="cuda", fp8=False, streams=1, nms=True, _outputs=None):
+        if fp8:
+            raise NotImplementedError("augment=True with fp8: the fp8 calibration is per compiled plan, and the "
+                                      "augmented session runs three; use half=True")
+        self.model, self.batch, self.h, self.w, self.dtype = model, batch, h, w, dtype
+        self.fp8, self.fp8_ready, self.fp8_calibration = False, False, None
+        self.conf, self.iou, self.max_det = float(conf), float(iou), int(max_det)
+        self.children, self.records, self._bound, self._graph = [], None, None, None
+        self.use_graph = use_graph
+        dev = torch.device(device)
+        det = model.model[-1]
+        nc = det.nc
+        multi_label = bool(multi_label) and nc > 1
+        self.passes = augment_passes(h, w, det.stride.tolist())
+        A = self.passes[-1][7] + self.passes[-1][6] - self.passes[-1][5]
+        self.A, self.nc, self.out_flat = A, nc, None
+        if _outputs is not None:  # slices of a split session's shared outputs
+            self.det, self.count, self.pred = _outputs
+        else:
+            self.pred = torch.empty((batch, 4 + nc, A), dtype=torch.float32, device=dev) if keep_pred else None
+            self.det, self.count, self.out_flat = _det_count(batch, self.max_det, dev)
+        if streams > 1 and batch >= streams:
+            from ..parallel import shard_bounds
+
+            self.bounds = [shard_bounds(batch, streams, r) for r in range(streams)]
+            for a, b in self.bounds:
+                outs = (self.det[a:b], self.count[a:b], self.pred[a:b] if keep_pred else None)
+                self.children.append(AugmentSession(model, b - a, h, w, dtype, conf, iou, max_det, multi_label,
+                                                    agnostic, classes, max_nms, max_wh, clip, keep_pred, use_graph,
+                                                    device, nms=nms, _outputs=outs))
+            self.streams = [torch.cuda.Stream(dev) for _ in self.children]
+            self.plans = [c.plan for c in self.children]
+            self.plan = self.plans[0]
+            return
+        from .preprocess import SCALE_IMG_PAD
+
+        cms = [model.compile(batch, hp, wp, dtype, device=dev) for _, _, _, (hp, wp), *_ in self.passes]
+        self.compiled_passes, self.compiled = cms, cms[0]  # (load() fills pass 0's staging buffer)
+        cap = A * nc if multi_label else A
+        self.cand_box = torch.empty((batch, cap, 4), dtype=torch.float32, device=dev)
+        self.cand_score = torch.empty((batch, cap), dtype=torch.float32, device=dev)
+        self.cand_cls = torch.empty((batch, cap), dtype=torch.int32, device=dev)
+        self.cand_idx = torch.empty((batch, cap), dtype=torch.int32, device=dev)
+        self.cand_count = torch.zeros((batch,), dtype=torch.int32, device=dev)
+        self.classes_t = (torch.tensor(list(classes), dtype=torch.int32, device=dev) if classes is not None else None)
+        ws = torch.zeros(int(_lib.lib.ydbl_nms_workspace(batch, cap, max_nms)), dtype=torch.uint8, device=dev)
+        plan = Plan(dev, dtype)
+        plan.buffers += [self.cand_box, self.cand_score, self.cand_cls, self.cand_idx, self.cand_count, self.det,
+                         self.count, ws]
+        ch = cms[0].input.shape[1]
+        for cm, (ratio, flip, (sh, sw), (hp, wp), *_) in zip(cms[1:], self.passes[1:]):
+            sd = ScaleImgDesc(cms[0].input.data_ptr(), batch, ch, h, w, sh, sw, hp, wp, int(flip), SCALE_IMG_PAD,
+                              cm.input.data_ptr())
+            plan.launch("ydbl_scale_img", sd, what=f"scale_img {ratio}", keep=[sd])
+        strides = (C.c_float * 3)(*[float(s) for s in det.stride.tolist()])
+        for i, (cm, (ratio, flip, _, _, A_i, a_lo, a_hi, pos)) in enumerate(zip(cms, self.passes)):
+            if sum(lv.h * lv.w for lv in cm.levels) != A_i:
+                raise RuntimeError(f"pass {i}: the compiled levels hold {sum(lv.h * lv.w for lv in cm.levels)} "
+                                   f"anchors, augment_passes() expects {A_i}")
+            plan.steps += cm.plan.steps
+            boxes = (View * 3)(*[lv.cslice(0, 64).struct() for lv in cm.levels])
+            clss = (View * 3)(*[lv.cslice(64, nc).struct() for lv in cm.levels])
+            dd = DecodeDesc(boxes, clss, len(cm.levels), nc, strides, self.conf, int(multi_label),
+                            self.classes_t.data_ptr() if self.classes_t is not None else None,
+                            len(self.classes_t) if self.classes_t is not None else 0,
+                            self.pred.data_ptr() if self.pred is not None else None,
+                            self.cand_box.data_ptr(), self.cand_score.data_ptr(), self.cand_cls.data_ptr(),
+                            self.cand_idx.data_ptr(), self.cand_count.data_ptr(), cap)
+            ga = DecodeAug(float(ratio), float(w) if flip else 0.0, a_lo, a_hi, pos, A, int(i > 0))
+            plan.launch("ydbl_detect_decode_aug", dd, ga, what=f"Detect.decode pass {i}", keep=[dd, ga])
+        nd = NmsDesc(self.cand_box.data_ptr(), self.cand_score.data_ptr(), self.cand_cls.data_ptr(),
+                     self.cand_idx.data_ptr(), self.cand_count.data_ptr(), batch, cap, self.iou, self.max_det,
+                     int(max_nms), int(bool(agnostic)), float(max_wh), float(w) if clip else 0.0,
+                     float(h) if clip else 0.0, self.det.data_ptr(), self.count.data_ptr(), ws.data_ptr(),
+                     self.det.stride(0), self.count.stride(0), int(self.conf >= PER_IMAGE_NMS_CONF))
+        if nms:
+            plan.launch("ydbl_nms", nd, what="NMS", keep=[nd])
+        self.plan, self.plans = plan, [plan]
+
+    def can_bind(self, x) -> bool:
+        """Never: scale_img reads pass 0's staging buffer, so predict() takes the copy path."""
+        return False
+
+    def calibrate_fp8(self, *a, **k):
+        raise NotImplementedError("augment=True has no fp8 path (the calibration is per compiled plan)")
+
+    def feats(self):
+        """None: the reference's augmented forward returns (y, None) (U/nn/tasks.py:376)."""
+        return None

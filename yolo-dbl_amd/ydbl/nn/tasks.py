@@ -205,12 +205,15 @@ class DetectionModel(nn.Module):
         Runs the compiled HIP plan of x's (batch, h, w, dtype) on x's device -- forward + decode, no NMS --
         replayed as a hipGraph; fp16 input takes the half path (AutoBackend fp16, autobackend.py:145-155).
         BN is folded and the semantics are always inference (eval) ones; training / loss (dict input) and
-        augment / profile / visualize / embed are not on this path.  Returns fresh tensors (the plan's buffers
-        are reused by the next call).  CPU tensors raise: there is no CPU execution path."""
+        profile / visualize / embed are not on this path.  augment=True: _predict_augment (U/nn/tasks.py:361-398) --
+        returns ``(y, None)``, y [B, 4+nc, A_tot] the three passes' de-scaled, de-flipped, tail-clipped predictions
+        side by side (engine.session.AugmentSession).  Returns fresh tensors (the plan's buffers are reused by the
+        next call).  CPU tensors raise: there is no CPU execution path."""
         if isinstance(x, dict):
             raise NotImplementedError("training loss (dict input) is outside the inference path")
-        if args or any(kwargs.get(k) for k in ("augment", "profile", "visualize", "embed")):
-            raise NotImplementedError("augment / profile / visualize / embed are outside the inference path")
+        if args or any(kwargs.get(k) for k in ("profile", "visualize", "embed")):
+            raise NotImplementedError("profile / visualize / embed are outside the inference path")
+        augment = bool(kwargs.get("augment"))
         if not isinstance(x, torch.Tensor) or x.ndim != 4:
             raise TypeError("DetectionModel.forward takes a BCHW tensor")
         if x.device.type != "cuda":
@@ -220,23 +223,25 @@ class DetectionModel(nn.Module):
         if x.shape[1] != self.yaml["ch"]:
             raise ValueError(f"input has {x.shape[1]} channels, the model {self.yaml['ch']}")
         b, _, h, w = x.shape
-        s = self._forward_session(b, h, w, x.dtype == torch.float16, x.device)
+        s = self._forward_session(b, h, w, x.dtype == torch.float16, x.device, augment=augment)
         s(x.float())
         sig = weights_signature(self)  # checked while the graph runs
         if sig != s.wsig:  # weights edited since the plan was compiled: rebuild, run again
-            s = self._forward_session(b, h, w, x.dtype == torch.float16, x.device, fresh=sig)
+            s = self._forward_session(b, h, w, x.dtype == torch.float16, x.device, fresh=sig, augment=augment)
             s(x.float())
         y = s.pred.to(x.dtype, copy=True)
+        if augment:
+            return y, None
         feats = [f.contiguous() for f in s.feats()]
         return y, feats
 
-    def _forward_session(self, b, h, w, half, device, fresh=None):
-        from ..engine.session import DetectSession, default_streams
+    def _forward_session(self, b, h, w, half, device, fresh=None, augment=False):
+        from ..engine.session import AugmentSession, DetectSession, default_streams
 
         cache = self.__dict__.setdefault("_fwd_sessions", {})
         # compiled plans hold the routing of the YDBL_* switches at build time (part of the key) and BN-folded
         # copies of the weights (the session's wsig, checked by forward() after each launch)
-        key = (b, h, w, half, str(device), ydbl_env())
+        key = (b, h, w, half, str(device), ydbl_env(), augment)
         s = cache.pop(key, None)
         if s is not None and fresh is not None and s.wsig != fresh:
             s = None  # weights changed since this plan was built
@@ -244,8 +249,9 @@ class DetectionModel(nn.Module):
             while len(cache) >= self.MAX_FORWARD_SESSIONS:
                 cache.pop(next(iter(cache)))
             with torch.cuda.device(device):
-                s = DetectSession(self, b, h, w, torch.float16 if half else torch.float32, keep_pred=True, nms=False,
-                                  device=device, streams=default_streams(b))
+                s = (AugmentSession if augment else DetectSession)(
+                    self, b, h, w, torch.float16 if half else torch.float32, keep_pred=True, nms=False,
+                    device=device, streams=default_streams(b))
             s.wsig = weights_signature(self)
         cache[key] = s  # most recently used last
         return s

@@ -90,7 +90,8 @@ def detections_list(det_all: torch.Tensor, count_all: torch.Tensor):
 class ShardedPredictor:
     """This rank's slice of a global batch through a compiled session whose NMS writes the record buffer, then
     the one all-gather into a preallocated global buffer.  Without an initialised process group it is the
-    plain session (world 1, no collective)."""
+    plain session (world 1, no collective).  augment=True is rejected (NotImplementedError from Model.session):
+    the test-time-augmentation session does not write record rows."""
 
     def __init__(self, model, global_batch: int, h: int, w: int, device, group=None, max_det: int = 300,
                  **session_kw):
