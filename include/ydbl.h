@@ -56,6 +56,8 @@
  *   ydbl_match_predictions <- DetectionValidator._process_batch models/yolo/detect/val.py:209-227
  *                             (box_iou utils/metrics.py:52-71 + BaseValidator.match_predictions
  *                             engine/validator.py:222-262, non-scipy branch)
+ *   ydbl_confusion_matrix  <- ConfusionMatrix.process_batch utils/metrics.py:326-382 and its call sites in
+ *                             DetectionValidator.update_metrics models/yolo/detect/val.py:140-159
  */
 #ifndef YDBL_H
 #define YDBL_H
@@ -472,6 +474,38 @@ typedef struct {
 } ydbl_match_desc;
 int64_t ydbl_match_workspace(int32_t n, int32_t max_det, int32_t n_gt, int32_t n_iou);
 int ydbl_match_predictions(const ydbl_match_desc* d, void* stream);
+
+/* Detection confusion matrix of a batch of NMS outputs against ground-truth labels, added into `matrix`:
+ * ConfusionMatrix.process_batch (utils/metrics.py:326-382) as DetectionValidator.update_metrics calls it per image
+ * (models/yolo/detect/val.py:140-159), with box_iou (utils/metrics.py:52-71) bitwise as ydbl_match_predictions
+ * evaluates it.  det / det_count / gt_box / gt_cls / gt_ofs as in ydbl_match_desc; classes are truncated to int
+ * like the reference's .int().  Row = predicted class, column = true class, index nc = background.  Per image:
+ *   kept detections: rows d < min(det_count, max_det) with det[d][4] > (float)conf;
+ *   a (label, detection) pair takes part when iou > (float)iou_thres (both compares strict, fp32);
+ *   best(d)   = the label with the largest participating IoU of detection d,
+ *   winner(l) = the detection with the largest iou(best(d), d) among those with best(d) == l;
+ *   label l with a winner: matrix[cls(winner(l))][cls(l)] += 1, without one: matrix[nc][cls(l)] += 1;
+ *   every kept detection that is no label's winner: matrix[cls(d)][nc] += 1.
+ * This is what the reference's two argsort / np.unique passes select.  Our rule on exact IoU ties: the larger
+ * label index wins best(d), the larger detection index wins winner(l) -- the order numpy's reversed argsort
+ * gives for match arrays of up to 16 rows (above that numpy's own order on ties is unspecified).
+ * A class outside [0, nc) on either side (the reference raises IndexError) writes nothing: that count is
+ * skipped and *invalid is incremented.  matrix int64 [(nc+1)][(nc+1)] and invalid int32 [1] are accumulated
+ * into (integer atomics: the result does not depend on scheduling); the caller zeroes them once per run.
+ * conf in any range, iou_thres >= 0, 1 <= nc <= 32767, max_det <= 2^20; workspace 8-byte aligned. */
+typedef struct {
+  const float* det; const int32_t* det_count;
+  int32_t n, max_det;
+  const float* gt_box; const float* gt_cls; const int32_t* gt_ofs;
+  int32_t n_gt;
+  int32_t nc;
+  float conf, iou_thres;
+  int64_t* matrix;
+  int32_t* invalid;
+  void* workspace; /* ydbl_confusion_workspace(n, max_det, n_gt) bytes */
+} ydbl_confusion_desc;
+int64_t ydbl_confusion_workspace(int32_t n, int32_t max_det, int32_t n_gt);
+int ydbl_confusion_matrix(const ydbl_confusion_desc* d, void* stream);
 
 const char* ydbl_last_error(void);
 const char* ydbl_version(void);

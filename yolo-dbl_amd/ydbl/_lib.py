@@ -135,6 +135,13 @@ class MatchDesc(C.Structure):
                 ("workspace", C.c_void_p)]
 
 
+class ConfusionDesc(C.Structure):
+    _fields_ = [("det", C.c_void_p), ("det_count", C.c_void_p), ("n", C.c_int32), ("max_det", C.c_int32),
+                ("gt_box", C.c_void_p), ("gt_cls", C.c_void_p), ("gt_ofs", C.c_void_p), ("n_gt", C.c_int32),
+                ("nc", C.c_int32), ("conf", C.c_float), ("iou_thres", C.c_float), ("matrix", C.c_void_p),
+                ("invalid", C.c_void_p), ("workspace", C.c_void_p)]
+
+
 # name -> (argtypes, restype); every entry must exist in include/ydbl.h
 _P = C.c_void_p
 _VP = C.POINTER(View)
@@ -185,6 +192,8 @@ SIGNATURES = {
     "ydbl_letterbox": ([C.POINTER(LetterboxDesc), _P], C.c_int),
     "ydbl_match_workspace": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32], C.c_int64),
     "ydbl_match_predictions": ([C.POINTER(MatchDesc), _P], C.c_int),
+    "ydbl_confusion_workspace": ([C.c_int32, C.c_int32, C.c_int32], C.c_int64),
+    "ydbl_confusion_matrix": ([C.POINTER(ConfusionDesc), _P], C.c_int),
     "ydbl_last_error": ([], C.c_char_p),
     "ydbl_version": ([], C.c_char_p),
 }

@@ -408,10 +408,15 @@ class Model:
     def val(self, data=None, **kwargs):
         """Detection mAP (U/engine/model.py:609-643): ``data`` = a data YAML, a dataset folder, an image folder /
         list, or in-memory batches; see ydbl.engine.validator.  rect batches by default, like the reference.
-        augment=True validates the test-time-augmented predictions (U/engine/validator.py: model(img, augment=...))."""
+        augment=True validates the test-time-augmented predictions (U/engine/validator.py: model(img, augment=...)).
+        plots (default True, as in the reference's default.yaml) accumulates ``metrics.confusion_matrix`` on the
+        device; False skips it.  No image files are written either way.  verbose=True prints the per-class table.
+        With save_dir, dataset-backed runs write predictions.json (save_json=True) and labels/<stem>.txt
+        (save_txt=True, save_conf for the confidence column); without save_dir nothing is written."""
         from .validator import DetectionValidator
 
-        args = {**DEFAULTS, "conf": 0.001, "iou": 0.7, "batch": 16, "rect": True, "split": "val", **kwargs}
+        args = {**DEFAULTS, "conf": 0.001, "iou": 0.7, "batch": 16, "rect": True, "split": "val", "plots": True,
+                "save_json": False, "save_txt": False, "save_conf": False, "save_dir": None, **kwargs}
         check_augment(args["augment"], args["fp8"])
         self.validator = DetectionValidator(self, args)  # kept: its per-image stats (tp, conf, pred_cls, target_cls)
         return self.validator(data)

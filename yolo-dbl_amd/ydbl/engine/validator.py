@@ -11,11 +11,18 @@ match_predictions) on the device with ydbl_match_predictions right behind NMS, t
   matched in native image space after scale_boxes(ratio_pad) (val.py:104-123), like the reference; or
 - an iterable of in-memory batches ``{"img": float [B,3,H,W] (0..1 or 0..255), "cls": [N], "bboxes": [N,4]
   xyxy pixels of the input image, "batch_idx": [N]}`` (boxes clipped to the input, gain 1 / pad 0).
+
+Beside the mean scalars the validator reports what the reference's does: ``metrics.confusion_matrix`` (counted on
+the device by ydbl_confusion_matrix on the tensors the TP matrix is matched on; ``plots=False`` skips it, as in
+the reference — no image files are written either way), the per-class table (``nt_per_class``, ``nt_per_image``,
+``seen``, ``print_results()``), and for dataset-backed runs with ``save_dir`` the ``predictions.json`` rows of
+``save_json`` and the ``labels/<stem>.txt`` files of ``save_txt`` / ``save_conf`` (no pycocotools evaluation).
 """
 
 from __future__ import annotations
 
 import ctypes as C
+import json
 import math
 import os
 from pathlib import Path
@@ -24,12 +31,55 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..utils.metrics import IOUV, DetMetrics
+from ..utils.metrics import IOUV, LOGGER, ConfusionMatrix, DetMetrics
 from .model import load_tensor_source, select_device
 
 
+def group_labels(gt_box, gt_cls, batch_idx, b: int, dev):
+    """A batch's labels grouped by image for the device kernels: (gt_box fp32 [N, 4], gt_cls fp32 [N], gt_ofs
+    int32 [b + 1], N) on dev.  Labels may arrive in any image order; the grouping is stable, so each image keeps
+    its own order, like the reference's per-image slice ``batch_idx == si``."""
+    bidx = torch.as_tensor(batch_idx).reshape(-1).long().cpu()
+    order = torch.argsort(bidx, stable=True)
+    ofs = torch.zeros(b + 1, dtype=torch.int32)
+    if len(bidx):
+        if int(bidx.min()) < 0 or int(bidx.max()) >= b:
+            raise ValueError(f"batch_idx must be in [0, {b})")
+        ofs[1:] = torch.cumsum(torch.bincount(bidx, minlength=b), 0).to(torch.int32)
+    boxes = torch.as_tensor(gt_box).reshape(-1, 4).float().cpu()[order].to(dev).contiguous()
+    cls = torch.as_tensor(gt_cls).reshape(-1).float().cpu()[order].to(dev).contiguous()
+    return boxes, cls, ofs.to(dev), len(bidx)
+
+
+def confusion_batch(det: torch.Tensor, count: torch.Tensor, gt_box, gt_cls, batch_idx, cm,
+                    single_cls: bool = False, grouped=None) -> None:
+    """Add one batch to a ydbl.utils.metrics.ConfusionMatrix on the device (ydbl_confusion_matrix): one launch
+    for ConfusionMatrix.process_batch (U/utils/metrics.py:326-382) over every image, as update_metrics calls it
+    (U/models/yolo/detect/val.py:140-159).  det / count / labels as for match_batch (``grouped``: the result of
+    group_labels, to share one grouping with it); single_cls counts every detection as class 0 (val.py:149-150).
+    Nothing is read back: ``cm.matrix`` does that."""
+    if det.device.type != "cuda":
+        raise RuntimeError("confusion_batch runs on the GPU (ydbl_confusion_matrix); got a CPU tensor")
+    dev = det.device
+    b, max_det = det.shape[0], det.shape[1]
+    boxes, cls, ofs, n_gt = grouped or group_labels(gt_box, gt_cls, batch_idx, b, dev)
+    det = det.float().contiguous()
+    if single_cls:
+        det = det.clone()
+        det[..., 5] = 0
+    count = count.to(dev, torch.int32).contiguous()
+    acc, invalid = cm.buffers(dev)
+    ws = torch.empty(int(_lib.lib.ydbl_confusion_workspace(b, max_det, n_gt)), dtype=torch.uint8, device=dev)
+    d = _lib.ConfusionDesc(det.data_ptr(), count.data_ptr(), b, max_det, boxes.data_ptr() if n_gt else None,
+                           cls.data_ptr() if n_gt else None, ofs.data_ptr(), n_gt, cm.nc, cm.conf, cm.iou_thres,
+                           acc.data_ptr(), invalid.data_ptr(), ws.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(_lib.lib.ydbl_confusion_matrix(C.byref(d), stream), "ydbl_confusion_matrix")
+
+
 def match_batch(det: torch.Tensor, count: torch.Tensor, gt_box: torch.Tensor, gt_cls: torch.Tensor,
-                batch_idx: torch.Tensor, iouv: torch.Tensor = IOUV, single_cls: bool = False) -> torch.Tensor:
+                batch_idx: torch.Tensor, iouv: torch.Tensor = IOUV, single_cls: bool = False,
+                grouped=None) -> torch.Tensor:
     """TP matrix of one batch on the device (ydbl_match_predictions).
 
     det fp32 [B, max_det, 6] and count int32 [B] as NMS leaves them; labels gt_box [N, 4] xyxy,
@@ -42,17 +92,7 @@ def match_batch(det: torch.Tensor, count: torch.Tensor, gt_box: torch.Tensor, gt
         raise RuntimeError("match_batch runs on the GPU (ydbl_match_predictions); got a CPU tensor")
     dev = det.device
     b, max_det = det.shape[0], det.shape[1]
-    bidx = torch.as_tensor(batch_idx).reshape(-1).long().cpu()
-    order = torch.argsort(bidx, stable=True)
-    ofs = torch.zeros(b + 1, dtype=torch.int32)
-    if len(bidx):
-        if int(bidx.min()) < 0 or int(bidx.max()) >= b:
-            raise ValueError(f"batch_idx must be in [0, {b})")
-        ofs[1:] = torch.cumsum(torch.bincount(bidx, minlength=b), 0).to(torch.int32)
-    n_gt = len(bidx)
-    boxes = torch.as_tensor(gt_box).reshape(-1, 4).float().cpu()[order].to(dev).contiguous()
-    cls = torch.as_tensor(gt_cls).reshape(-1).float().cpu()[order].to(dev).contiguous()
-    ofs = ofs.to(dev)
+    boxes, cls, ofs, n_gt = grouped or group_labels(gt_box, gt_cls, batch_idx, b, dev)
     iouv_d = iouv.float().to(dev).contiguous()
     det = det.float().contiguous()
     count = count.to(dev, torch.int32).contiguous()
@@ -78,16 +118,51 @@ class DetectionValidator:
             raise ValueError("val(data=...) needs a data YAML, an image folder, or an iterable of batches")
         dev = select_device(self.args.get("device"))
         self.stats = {"tp": [], "conf": [], "pred_cls": [], "target_cls": []}
+        self.target_img = []  # per image with labels or predictions: its distinct label classes (val.py:139)
         self.seen = 0
+        self.nc = len(self.model.names)
+        self.confusion_matrix = ConfusionMatrix(nc=self.nc, conf=self.args["conf"])  # val.py:83
+        self.jdict = []
+        self.save_dir = Path(self.args["save_dir"]) if self.args.get("save_dir") else None
         if isinstance(data, (str, os.PathLike, dict)):
             self._run_dataset(data, dev)
         else:
             for batch in data:
                 self._run_tensor_batch(batch, dev)
         st = {k: torch.cat(v, 0).numpy() if v else np.zeros((0, 10) if k == "tp" else 0) for k, v in self.stats.items()}
+        # get_stats (val.py:179-187)
+        self.nt_per_class = np.bincount(st["target_cls"].astype(int), minlength=self.nc)
+        timg = torch.cat(self.target_img).numpy() if self.target_img else np.zeros(0)
+        self.nt_per_image = np.bincount(timg.astype(int), minlength=self.nc)
         if len(st["tp"]) and st["tp"].any():
             self.metrics.process(st["tp"], st["conf"], st["pred_cls"], st["target_cls"])
+        self.metrics.confusion_matrix = self.confusion_matrix  # finalize_metrics (val.py:174-177)
+        if self.save_dir is not None and self.args.get("save_json") and self.jdict:
+            self.save_dir.mkdir(parents=True, exist_ok=True)
+            with open(self.save_dir / "predictions.json", "w") as f:  # U/engine/validator.py:205-208
+                json.dump(self.jdict, f)
+        if self.args.get("verbose"):
+            print("\n".join([self.get_desc(), *self.print_results()]))
         return self.metrics
+
+    def get_desc(self):
+        """val.py:88-90: the table header of this fork (mAP75 is its fifth metric column)."""
+        return ("%22s" + "%11s" * 7) % ("Class", "Images", "Instances", "Box(P", "R", "mAP50", "mAP75", "mAP50-95)")
+
+    def print_results(self):
+        """val.py:189-201: the 'all' line and, for nc > 1, one line per class that has labels; logged to the
+        'ydbl' logger and returned (val(verbose=True) prints them under get_desc())."""
+        pf = "%22s" + "%11i" * 2 + "%11.3g" * len(self.metrics.keys)
+        lines = [pf % ("all", self.seen, self.nt_per_class.sum(), *self.metrics.mean_results())]
+        if self.nt_per_class.sum() == 0:
+            LOGGER.warning("no labels found in the val set, can not compute metrics without labels")
+        if self.nc > 1:
+            for i, c in enumerate(self.metrics.ap_class_index):
+                lines.append(pf % (self.model.names[c], self.nt_per_image[c], self.nt_per_class[c],
+                                   *self.metrics.class_result(i)))
+        for ln in lines:
+            LOGGER.info(ln)
+        return lines
 
     def _session(self, b, h, w, dev, clip):
         a = self.args
@@ -144,14 +219,22 @@ class DetectionValidator:
             _scale_clip(det_n[..., :4], pad[:, None, :], gain[:, None, None], ori[:, None, :])
             bidx = torch.from_numpy(hb["batch_idx"]).long()
             native = native_labels(hb)
-            self._update(det_n, cnt_d, native, torch.from_numpy(hb["cls"]).float(), bidx)
+            self._update(det_n, cnt_d, native, torch.from_numpy(hb["cls"]).float(), bidx,
+                         im_files=hb["im_file"], ori_shapes=hb["ori_shape"])
 
-    def _update(self, det_d, cnt_d, box_all, cls_all, bidx):
-        """update_metrics (val.py:125-172) for one batch: device TP matrix, host stats in image order."""
+    def _update(self, det_d, cnt_d, box_all, cls_all, bidx, im_files=None, ori_shapes=None):
+        """update_metrics (val.py:125-172) for one batch: device TP matrix and confusion counts (one launch each on
+        one label grouping), host stats in image order, and for dataset batches the predictions.json rows / label
+        files of save_json / save_txt."""
         b = det_d.shape[0]
         single = bool(self.args.get("single_cls", False))
-        tp_all = match_batch(det_d, cnt_d, box_all, cls_all, bidx, self.iouv, single).cpu()
+        grouped = group_labels(box_all, cls_all, bidx, b, det_d.device)
+        tp_all = match_batch(det_d, cnt_d, box_all, cls_all, bidx, self.iouv, single, grouped=grouped)
+        if self.args.get("plots", True):  # val.py:144-145, :158-159
+            confusion_batch(det_d, cnt_d, box_all, cls_all, bidx, self.confusion_matrix, single, grouped=grouped)
+        tp_all = tp_all.cpu()
         det, cnt = det_d.cpu(), cnt_d.cpu().tolist()
+        save = self.save_dir is not None and im_files is not None
         for si in range(b):
             self.seen += 1
             pred = det[si, : cnt[si]]
@@ -163,6 +246,7 @@ class DetectionValidator:
                     self.stats["conf"].append(torch.zeros(0))
                     self.stats["pred_cls"].append(torch.zeros(0))
                     self.stats["target_cls"].append(cls)
+                    self.target_img.append(cls.unique())
                 continue
             if single:
                 pred[:, 5] = 0
@@ -170,6 +254,37 @@ class DetectionValidator:
             self.stats["conf"].append(pred[:, 4])
             self.stats["pred_cls"].append(pred[:, 5])
             self.stats["target_cls"].append(cls)
+            self.target_img.append(cls.unique())
+            if save and self.args.get("save_json"):
+                self.jdict.extend(pred_to_json(pred, im_files[si]))
+            if save and self.args.get("save_txt"):
+                save_one_txt(pred, bool(self.args.get("save_conf", False)), ori_shapes[si], self.model.names,
+                             self.save_dir / "labels" / f"{Path(im_files[si]).stem}.txt")
+
+
+def pred_to_json(predn: torch.Tensor, filename, class_map=None) -> list:
+    """pred_to_json (val.py:281-295): one COCO-format row per detection of one image.  A numeric stem becomes an
+    int image_id; category_id = class_map[class] (default class + 1, val.py:77); bbox = top-left xywh rounded to
+    3 places; score rounded to 5."""
+    stem = Path(filename).stem
+    image_id = int(stem) if stem.isnumeric() else stem
+    box = torch.empty_like(predn[:, :4])  # xyxy2xywh (U/utils/ops.py:395-413), then centre -> top-left
+    box[:, 0] = (predn[:, 0] + predn[:, 2]) / 2
+    box[:, 1] = (predn[:, 1] + predn[:, 3]) / 2
+    box[:, 2] = predn[:, 2] - predn[:, 0]
+    box[:, 3] = predn[:, 3] - predn[:, 1]
+    box[:, :2] -= box[:, 2:] / 2
+    return [{"image_id": image_id, "category_id": class_map[int(p[5])] if class_map else int(p[5]) + 1,
+             "bbox": [round(x, 3) for x in b], "score": round(p[4], 5)}
+            for p, b in zip(predn.tolist(), box.tolist())]
+
+
+def save_one_txt(predn: torch.Tensor, save_conf: bool, shape, names, file) -> None:
+    """save_one_txt (val.py:270-279): 'cls xc yc w h [conf]' rows normalized by the original (h, w), appended."""
+    from .results import Results
+
+    Results(None, path=None, names=names, boxes=predn[:, :6], orig_shape=(shape[0], shape[1])).save_txt(
+        file, save_conf=save_conf)
 
 
 def native_labels(hb) -> torch.Tensor:
