@@ -16,7 +16,16 @@
 //      Detect class conv tail of conv_common.hpp when one wave holds all 64 output channels).
 // Two barriers per launch.  Every rounding and every accumulation order is dsconv.hip's (taps and halo
 // rounded to the activation dtype, k-steps in channel order), so the outputs are bit-identical to it
-// (tests/test_gpu_ops.py::test_dsconv_lean_bit_identical).
+// (tests/test_gpu_ops.py::test_dsconv_lean_bit_identical); the depthwise values themselves are pinned to a CPU
+// restatement (tests/test_gpu_depthwise_pairs.py).
+//
+// One image per workgroup.  Two images per workgroup for the 64-channel stride-1 tiles (taps, bias and A
+// fragments loaded once; k3: both halos resident, 47 KB of LDS, a thread owns a whole 8-pixel row, 146 VGPRs,
+// 3 workgroups per CU; k7: one halo buffer refilled from registers + two B tiles, 56 KB, 221 registers, 2
+// workgroups per CU) was built, bit-identical, and lost: per bs16 launch at 40^2 k3 6.43 -> 6.52 us, k7 10.12 ->
+// 11.44 us, DBL-n bs32 -0.5 % (k3 alone), -0.9 % (k7 alone), -0.8 % (both).  Half as many workgroups, each
+// twice as long and with fewer waves to hide its barriers behind, cost more than the shared weight loads
+// saved (profiles/r10/r10_partB_two_images.txt).
 #include <stdlib.h>
 
 #include "dsc_lean.hpp"

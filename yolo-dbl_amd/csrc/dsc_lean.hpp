@@ -45,7 +45,12 @@ __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const flo
   // per wave: a group of TN output-channel tiles (<= 64 channels; fewer for deep inputs, whose A fragments
   // [TN][NKS] would not fit the VGPRs); all 64 when CO = 64 and C <= 128 (the Detect class-conv tail needs them)
   constexpr int TNA = 16 / NKS < 1 ? 1 : 16 / NKS;
-  constexpr int TN = NTC < (TNA < 4 ? TNA : 4) ? NTC : (TNA < 4 ? TNA : 4);
+  constexpr int TN0 = NTC < (TNA < 4 ? TNA : 4) ? NTC : (TNA < 4 ? TNA : 4);
+  // 64 -> 64 without the tail: a wave owns ONE 16-channel tile over all four pixel tiles instead of all 64 channels
+  // of one pixel tile.  A quarter of the pointwise matrix per wave (8 KB per workgroup from L2 instead of 32 KB,
+  // 8 VGPRs of A fragments instead of 32) for six more ds_read_b128 of the B tile; same MFMA chain per output.
+  // bs16 at 40^2 in graph: k3 6.40 -> 5.62 us, k7 9.94 -> 9.08 us (profiles/r10/r10_partC_ab.txt).
+  constexpr int TN = (C == 64 && CO == 64 && !TAIL) ? 1 : TN0;
   constexpr int NCG = NTC / TN;
   static_assert(NTC % TN == 0 && WAVES % NCG == 0, "channel groups over waves");
   constexpr int WPG = WAVES / NCG;
@@ -174,30 +179,70 @@ __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const flo
       const int r = (tid / NQ) % TH;
       const int sg = tid / (NQ * TH);
       float a[CSEG][4];
-#pragma unroll
-      for (int c = 0; c < CSEG; ++c)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) a[c][e] = 0.f;
       constexpr int KU = K <= 3 ? K : 1;  // the 7x7: one input row's window + taps live at a time
+      if constexpr (C <= 64) {
+        // Window, taps and accumulators as explicit channel pairs (e0,e1), (e2,e3): one v_pk_fma_f32 per pair with
+        // its operands already in adjacent registers.  Written as scalar fmaf over [4] (below), the SLP vectoriser
+        // also packs, but across the quad's natural pairs, and pays a quarter of the loop's VALU issue in v_mov_b32
+        // to build them.  Each lane of a packed fma is the same IEEE fma: the (ky, kx) chain per channel is unchanged.
+        f32x2 a2[CSEG][2];
+#pragma unroll
+        for (int c = 0; c < CSEG; ++c) a2[c][0] = a2[c][1] = f32x2{0.f, 0.f};
 #pragma unroll KU
-      for (int ky = 0; ky < K; ++ky) {
-        const h4* xrow = &s_x[((r * S + ky) * IWP + sg * CSEG * S) * NQ + q];
-        float xs[SEGW][4];
+        for (int ky = 0; ky < K; ++ky) {
+          const h4* xrow = &s_x[((r * S + ky) * IWP + sg * CSEG * S) * NQ + q];
+          f32x2 xs[SEGW][2];
 #pragma unroll
-        for (int i = 0; i < SEGW; ++i) {
-          const h4 v = xrow[i * NQ];
+          for (int i = 0; i < SEGW; ++i) {
+            const h4 v = xrow[i * NQ];
+            xs[i][0] = f32x2{float(v[0]), float(v[1])};
+            xs[i][1] = f32x2{float(v[2]), float(v[3])};
+          }
+          f32x2 wv[K][2];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) xs[i][e] = float(v[e]);
+          for (int kx = 0; kx < K; ++kx) {
+            const f32x4 w = s_w[(ky * K + kx) * NQ + q];
+            wv[kx][0] = w.lo;
+            wv[kx][1] = w.hi;
+          }
+#pragma unroll
+          for (int kx = 0; kx < K; ++kx)
+#pragma unroll
+            for (int c = 0; c < CSEG; ++c)
+#pragma unroll
+              for (int h = 0; h < 2; ++h) a2[c][h] = __builtin_elementwise_fma(xs[c * S + kx][h], wv[kx][h], a2[c][h]);
         }
-        f32x4 wv[K];
 #pragma unroll
-        for (int kx = 0; kx < K; ++kx) wv[kx] = s_w[(ky * K + kx) * NQ + q];
+        for (int c = 0; c < CSEG; ++c)
 #pragma unroll
-        for (int kx = 0; kx < K; ++kx)
+          for (int e = 0; e < 4; ++e) a[c][e] = a2[c][e >> 1][e & 1];
+      } else {
+        // the 512-thread tiles keep the scalar form: with pairs they take fewer registers (k3 188 -> 138, stride 2
+        // 170 -> 123) and more waves per SIMD, and DBL-s bs8, which runs them at 40^2, lost 0.5 % (profiles/r10/)
 #pragma unroll
-          for (int c = 0; c < CSEG; ++c)
+        for (int c = 0; c < CSEG; ++c)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) a[c][e] = fmaf(xs[c * S + kx][e], wv[kx][e], a[c][e]);
+          for (int e = 0; e < 4; ++e) a[c][e] = 0.f;
+#pragma unroll KU
+        for (int ky = 0; ky < K; ++ky) {
+          const h4* xrow = &s_x[((r * S + ky) * IWP + sg * CSEG * S) * NQ + q];
+          float xs[SEGW][4];
+#pragma unroll
+          for (int i = 0; i < SEGW; ++i) {
+            const h4 v = xrow[i * NQ];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) xs[i][e] = float(v[e]);
+          }
+          f32x4 wv[K];
+#pragma unroll
+          for (int kx = 0; kx < K; ++kx) wv[kx] = s_w[(ky * K + kx) * NQ + q];
+#pragma unroll
+          for (int kx = 0; kx < K; ++kx)
+#pragma unroll
+            for (int c = 0; c < CSEG; ++c)
+#pragma unroll
+              for (int e = 0; e < 4; ++e) a[c][e] = fmaf(xs[c * S + kx][e], wv[kx][e], a[c][e]);
+        }
       }
       if (dwb) {  // uniform: DWConv (+ folded BN) bias and activation before the pointwise
         const f32x4 bq = *reinterpret_cast<const f32x4*>(dwb + q * 4);
