@@ -36,7 +36,10 @@
  *   ydbl_conv_stem2        <- preprocess + the backbone's first two Convs (layers 0-1 of the DBL yamls:
  *                             Conv(3,C0,3,1) -> Conv(C0,2*C0,3,2), conv.py:39-63 after fuse), fp16
  *   ydbl_gate_add          <- FullPAD_Tunnel.forward nn/modules/block.py:1954-1956
- *   ydbl_pool_up_concat    <- FuseModule.forward block.py:1831-1840, DownsampleConv block.py:1927
+ *   ydbl_channel_gate_add  <- A2C2f.forward block.py:1404-1405 (x + gamma * y)
+ *   ydbl_area_attn         <- AAttn.forward block.py:1243-1264 (softmax(q^T k / sqrt(32)) v per area chunk)
+ *   ydbl_pool_up_concat    <- FuseModule.forward block.py:1831-1840, DownsampleConv block.py:1927,
+ *                             nn.Upsample(scale_factor=2, mode="nearest")
  *   ydbl_dysample(_ex)     <- DySample.sample modules_upsample/DySample.py:48-61 (grid_sample border)
  *   ydbl_dysample2         <- DySample.forward DySample.py:63-81 (offset conv + sample, one launch)
  *   ydbl_lsk_gate          <- LSKblock.forward LSKA.py:40-52 (mean/max, 7x7 squeeze, sigmoid gating)
@@ -193,6 +196,26 @@ int ydbl_conv_stem(const float* x, int32_t n, int32_t cin, int32_t h, int32_t w,
 
 /* y = a + gate * b (FullPAD_Tunnel). */
 int ydbl_gate_add(const ydbl_view* a, const ydbl_view* b, float gate, const ydbl_view* y, void* stream);
+
+/* y = a + gate[c] * b, gate an fp32 device vector [c], 16-byte aligned (A2C2f's residual x + gamma * y). */
+int ydbl_channel_gate_add(const ydbl_view* a, const ydbl_view* b, const float* gate, const ydbl_view* y,
+                          void* stream);
+
+/* AAttn's attention core (U/nn/modules/block.py:1243-1264), head_dim 32.
+ * qkv: [n,h,w,3*C] NHWC view, C = heads*32, channel = head*96 + {q 0..31 | k 32..63 | v 64..95}.
+ * The h*w tokens of an image, in row-major order, form `area` contiguous chunks of T = h*w/area tokens;
+ * for each (image, chunk, head): P = softmax(q k^T * scale) over the chunk's T keys, y = P v.
+ * y: [n,h,w,C] view, channel = head*32 + d.  v: the V part re-laid the same way (the input of AAttn.pe),
+ * or a null view (ptr NULL) to skip it.  h*w % area != 0 is an error (the reference's reshape fails too).
+ * Any T >= 1: key / value tiles stream through LDS with an online softmax.  f16: f16 MFMA, fp32 maximum, sum and
+ * accumulators, P rounded to f16 for P v; f32: the fp32 MFMA.  All views 16-byte aligned channel vectors;
+ * y and v must not overlap qkv.  n * area * heads <= 65535. */
+typedef struct {
+  ydbl_view qkv, y, v;
+  int32_t heads, area;
+  float scale;
+} ydbl_area_attn_desc;
+int ydbl_area_attn(const ydbl_area_attn_desc* d, void* stream);
 
 /* y[..., off0:] = avgpool2(p_lo); y[..., off1:] = p_mid; y[..., off2:] = nearest_up2(p_hi).
  * Any of p_lo / p_mid / p_hi may be NULL (DownsampleConv uses p_lo only). */

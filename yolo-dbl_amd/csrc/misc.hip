@@ -328,6 +328,29 @@ __global__ __launch_bounds__(256) void gate_add_kernel(DView<const T> a, DView<c
   store_f<V>(y.pix(pix) + c0, o);
 }
 
+// ------------------------------------------------------------------ A2C2f residual: y = a + g[c] * b
+template <typename T>
+__global__ __launch_bounds__(256) void channel_gate_add_kernel(DView<const T> a, DView<const T> bv,
+                                                               const float* __restrict__ gate, DView<T> y) {
+  constexpr int V = Vec<T>::N;
+  const int cg = y.c / V;
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)y.n * y.h * y.w * cg) return;
+  const int c0 = (int)(idx % cg) * V;
+  const int64_t pix = idx / cg;
+  float av[V], b2[V], gv[V], o[V];
+  load_f<V>(a.pix(pix) + c0, av);
+  load_f<V>(bv.pix(pix) + c0, b2);
+  load_f<V>(gate + c0, gv);
+#pragma unroll
+  for (int q = 0; q < V; ++q) {
+    float t = gv[q] * b2[q];  // the product rounded on its own, as gamma * y is in the reference: no fma
+    asm volatile("" : "+v"(t));
+    o[q] = add_rn(av[q], t);
+  }
+  store_f<V>(y.pix(pix) + c0, o);
+}
+
 // ------------------------------------------------------------------ FuseModule / DownsampleConv input
 template <typename T>
 __global__ __launch_bounds__(256) void pool_up_concat_kernel(DView<const T> lo, DView<const T> mid,
@@ -628,6 +651,24 @@ extern "C" int ydbl_gate_add(const ydbl_view* a, const ydbl_view* b, float gate,
   else
     gate_add_kernel<float><<<nblk(total), 256, 0, s>>>(cview<float>(a), cview<float>(b), gate, dview<float>(*y));
   return check_launch("ydbl_gate_add");
+}
+
+extern "C" int ydbl_channel_gate_add(const ydbl_view* a, const ydbl_view* b, const float* gate, const ydbl_view* y,
+                                     void* stream) {
+  if (check_view(a, "cgate.a", true) || check_view(b, "cgate.b", true) || check_view(y, "cgate.y", true)) return YDBL_EINVAL;
+  if (!gate || reinterpret_cast<uintptr_t>(gate) % 16) return fail(YDBL_EINVAL, "channel_gate_add: gate must be a 16-byte aligned fp32 vector");
+  if (a->c != y->c || b->c != y->c || a->n * a->h * a->w != y->n * y->h * y->w ||
+      b->n * b->h * b->w != y->n * y->h * y->w || a->dtype != y->dtype || b->dtype != y->dtype)
+    return fail(YDBL_EINVAL, "channel_gate_add: shape mismatch");
+  hipStream_t s = as_stream(stream);
+  const int V = y->dtype == YDBL_F16 ? 8 : 4;
+  const int64_t total = (int64_t)y->n * y->h * y->w * (y->c / V);
+  if (y->dtype == YDBL_F16)
+    channel_gate_add_kernel<_Float16><<<nblk(total), 256, 0, s>>>(cview<_Float16>(a), cview<_Float16>(b), gate,
+                                                                   dview<_Float16>(*y));
+  else
+    channel_gate_add_kernel<float><<<nblk(total), 256, 0, s>>>(cview<float>(a), cview<float>(b), gate, dview<float>(*y));
+  return check_launch("ydbl_channel_gate_add");
 }
 
 extern "C" int ydbl_pool_up_concat(const ydbl_view* lo, const ydbl_view* mid, const ydbl_view* hi, const ydbl_view* y,

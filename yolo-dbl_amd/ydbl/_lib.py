@@ -142,6 +142,11 @@ class ConfusionDesc(C.Structure):
                 ("invalid", C.c_void_p), ("workspace", C.c_void_p)]
 
 
+class AreaAttnDesc(C.Structure):
+    _fields_ = [("qkv", View), ("y", View), ("v", View), ("heads", C.c_int32), ("area", C.c_int32),
+                ("scale", C.c_float)]
+
+
 # name -> (argtypes, restype); every entry must exist in include/ydbl.h
 _P = C.c_void_p
 _VP = C.POINTER(View)
@@ -159,6 +164,8 @@ SIGNATURES = {
     "ydbl_conv_stem": ([_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P, C.c_int32, C.c_int32,
                         C.c_int32, _VP, C.POINTER(InputBind), _P], C.c_int),
     "ydbl_gate_add": ([_VP, _VP, C.c_float, _VP, _P], C.c_int),
+    "ydbl_channel_gate_add": ([_VP, _VP, _P, _VP, _P], C.c_int),
+    "ydbl_area_attn": ([C.POINTER(AreaAttnDesc), _P], C.c_int),
     "ydbl_pool_up_concat": ([_VP, _VP, _VP, _VP, _P], C.c_int),
     "ydbl_dysample": ([_VP, _VP, C.c_int32, _VP, _P], C.c_int),
     "ydbl_dysample_ex": ([C.POINTER(DySampleDesc), _P], C.c_int),

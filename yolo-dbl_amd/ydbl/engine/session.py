@@ -92,6 +92,9 @@ class DetectSession:
                  fp8_calibration=None, _outputs=None, _bind=None):
         if fp8 and dtype != torch.float16:
             raise ValueError("fp8 operands run on the fp16 activation path (half=True)")
+        if fp8 and any(type(m).__name__ == "A2C2f" for m in model.modules()):
+            raise NotImplementedError("fp8=True on a model with A2C2f: no calibration record exists for the "
+                                      "area-attention blocks")
         self.model, self.batch, self.h, self.w, self.dtype = model, batch, h, w, dtype
         self.fp8, self.fp8_ready = bool(fp8), False
         self.fp8_calibration = fp8_calibration  # an Fp8Calibration / its file, applied at the first launch

@@ -170,9 +170,35 @@ def emit_conv2d(plan: Plan, conv: nn.Conv2d, x: TV, out: TV | None, weight=None,
         if res_mode not in (_lib.RES_NONE, _lib.RES_ADD):
             raise NotImplementedError("depthwise conv supports residual ADD only")
         emit_dw(plan, x, y, w, b, s, p, d, act, res if res_mode == _lib.RES_ADD else None, what)
+    elif conv.in_channels % conv.groups == 0 and conv.out_channels % conv.groups == 0 and x.c == conv.in_channels:
+        emit_grouped(plan, x, y, w, b, conv.groups, s, p, d, act, res, res_mode, what)
     else:
-        raise NotImplementedError(f"grouped conv g={conv.groups} is not on the DBL path")
+        raise NotImplementedError(f"grouped conv g={conv.groups} with {x.c} -> {conv.out_channels} channels")
     return y
+
+
+def emit_grouped(plan: Plan, x: TV, y: TV, w: torch.Tensor, b: torch.Tensor | None, groups: int, stride=1, pad=0,
+                 dil=1, act=_lib.ACT_NONE, res: TV | None = None, res_mode=_lib.RES_NONE, what="conv"):
+    """Grouped dense conv (1 < groups < cin; yolov13.yaml's Conv [.., 3, 2, 1, g]); w fp32 [co, ci/groups, kh, kw].
+    One dense launch per group on channel slices of x, y (and res) with that group's weight rows, when every slice
+    keeps the dense entry point's rules (16-byte channel vectors, cin % 8); else one dense launch with
+    block-diagonal, zero-filled weights.  The same sums either way.  A per-group launch registers its own slice
+    as written (note_writer), never y: a FullPAD_Tunnel on y then takes its own launch."""
+    co, cig = w.shape[0], w.shape[1]
+    cog = co // groups
+    xs = [x.cslice(i * cig, cig) for i in range(groups)]
+    ys = [y.cslice(i * cog, cog) for i in range(groups)]
+    rs = [res.cslice(i * cog, cog) if res is not None else None for i in range(groups)]
+    if cig % 8 == 0 and all(vec_aligned(v) for v in (*xs, *ys, *(r for r in rs if r is not None))):
+        for i in range(groups):
+            rows = slice(i * cog, (i + 1) * cog)
+            emit_dense(plan, xs[i], ys[i], w[rows], b[rows] if b is not None else None, stride, pad, dil, act, rs[i],
+                       res_mode, f"{what}.g{i}/{groups}")
+        return
+    full = torch.zeros((co, cig * groups, *w.shape[2:]), dtype=w.dtype)
+    for i in range(groups):
+        full[i * cog:(i + 1) * cog, i * cig:(i + 1) * cig] = w[i * cog:(i + 1) * cog]
+    emit_dense(plan, x, y, full, b, stride, pad, dil, act, res, res_mode, f"{what}.g{groups}dense")
 
 
 def fused_dsconv_ok(dw: nn.Conv2d, x: TV, dtype) -> bool:
@@ -762,6 +788,121 @@ class DSC3k2(C2f):
             self.m = nn.ModuleList(
                 DSBottleneck(self.c, self.c, shortcut=shortcut, e=1.0, k1=k1, k2=k2, d2=d2) for _ in range(n)
             )
+
+
+class AAttn(PlanModule):
+    """U/nn/modules/block.py:1187-1264 — area attention: qkv 1x1 -> softmax(q^T k / sqrt(d)) v inside each of the
+    `area` contiguous token chunks (ydbl_area_attn) -> + pe(v) (7x7 depthwise) -> proj 1x1."""
+
+    def __init__(self, dim, num_heads, area=1):
+        super().__init__()
+        self.area = area
+        self.num_heads = num_heads
+        self.head_dim = head_dim = dim // num_heads
+        all_head_dim = head_dim * self.num_heads
+        self.qkv = Conv(dim, all_head_dim * 3, 1, act=False)
+        self.proj = Conv(all_head_dim, dim, 1, act=False)
+        self.pe = Conv(all_head_dim, dim, 7, 1, 3, g=dim, act=False)
+
+    def emit(self, plan, x, out=None, res=None):
+        """res: a view added to the result in proj's epilogue (ABlock's x + attn(x))."""
+        if self.head_dim != 32:
+            raise NotImplementedError(f"AAttn: head_dim {self.head_dim}; the HIP kernel is built for 32 (A2C2f's)")
+        if (x.h * x.w) % self.area:
+            raise ValueError(f"AAttn: {x.h}x{x.w} tokens do not split into {self.area} areas")
+        c = self.num_heads * self.head_dim
+        qkv = self.qkv.emit(plan, x)
+        att, v = plan.alloc(x.n, x.h, x.w, c), plan.alloc(x.n, x.h, x.w, c)
+        d = _lib.AreaAttnDesc(qkv.struct(), att.struct(), v.struct(), self.num_heads, self.area, self.head_dim**-0.5)
+        plan.launch("ydbl_area_attn", d, what=f"AAttn.area{self.area}", keep=[d])
+        t = self.pe.emit(plan, v, None, res=att, res_mode=_lib.RES_ADD)  # x + pe(v)
+        return self.proj.emit(plan, t, out, res=res, res_mode=_lib.RES_ADD if res is not None else _lib.RES_NONE)
+
+
+class ABlock(PlanModule):
+    """U/nn/modules/block.py:1268-1322 — x + attn(x), then x + mlp(x); both adds ride in conv epilogues."""
+
+    def __init__(self, dim, num_heads, mlp_ratio=1.2, area=1):
+        super().__init__()
+        self.attn = AAttn(dim, num_heads=num_heads, area=area)
+        mlp_hidden_dim = int(dim * mlp_ratio)
+        self.mlp = nn.Sequential(Conv(dim, mlp_hidden_dim, 1), Conv(mlp_hidden_dim, dim, 1, act=False))
+        self.apply(self._init_weights)
+
+    @staticmethod
+    def _init_weights(m):
+        if isinstance(m, nn.Conv2d):
+            nn.init.trunc_normal_(m.weight, std=0.02)
+            if m.bias is not None:
+                nn.init.constant_(m.bias, 0)
+
+    def emit(self, plan, x, out=None):
+        x1 = self.attn.emit(plan, x, None, res=x)
+        (w0, b0), (w1, b1) = self.mlp[0].folded(), self.mlp[1].folded()
+        hid = w0.shape[0]
+        pad = round_up(hid, 8) - hid  # int(dim * mlp_ratio) need not be whole channel vectors (128 * 1.2 = 153):
+        if pad:  # zero output rows make the pad channels SiLU(0) = 0, and mlp[1]'s K is zero-padded to match
+            w0 = torch.nn.functional.pad(w0, (0, 0, 0, 0, 0, 0, 0, pad))
+            b0 = torch.nn.functional.pad(b0 if b0 is not None else torch.zeros(hid), (0, pad))
+        h = plan.alloc(x.n, x.h, x.w, hid + pad)
+        emit_dense(plan, x1, h, w0, b0, act=_act_code(self.mlp[0].act), what="Conv1x1")
+        y = out if out is not None else plan.alloc(x.n, x.h, x.w, x.c)
+        emit_dense(plan, h, y, w1, b1, act=_act_code(self.mlp[1].act), res=x1, res_mode=_lib.RES_ADD, what="Conv1x1")
+        return y
+
+
+class A2C2f(PlanModule):
+    """U/nn/modules/block.py:1325-1406 — cv1, n x (ABlock, ABlock) chained through the slices of one concat buffer,
+    cv2; residual=True: x + gamma[c] * y (ydbl_channel_gate_add: cv2 has a SiLU, gamma does not fold into it)."""
+
+    def __init__(self, c1, c2, n=1, a2=True, area=1, residual=False, mlp_ratio=2.0, e=0.5, g=1, shortcut=True):
+        super().__init__()
+        c_ = int(c2 * e)
+        assert c_ % 32 == 0, "Dimension of ABlock must be a multiple of 32."
+        if not a2:
+            raise NotImplementedError("A2C2f(a2=False), the C3k form, has no HIP path (no v13 config uses it)")
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv((1 + n) * c_, c2, 1)
+        self.gamma = nn.Parameter(0.01 * torch.ones(c2), requires_grad=True) if a2 and residual else None
+        self.m = nn.ModuleList(
+            nn.Sequential(*(ABlock(c_, c_ // 32, mlp_ratio, area) for _ in range(2))) for _ in range(n))
+
+    def emit(self, plan, x, out=None):
+        c_, n = self.cv1.conv.out_channels, len(self.m)
+        buf = plan.alloc(x.n, x.h, x.w, (1 + n) * c_)
+        self.cv1.emit(plan, x, buf.cslice(0, c_))
+        for i, m in enumerate(self.m):
+            emit_seq(plan, m, buf.cslice(i * c_, c_), buf.cslice((i + 1) * c_, c_))
+        if self.gamma is None:
+            return self.cv2.emit(plan, buf, out)
+        t = self.cv2.emit(plan, buf)
+        y = out if out is not None else plan.alloc(x.n, x.h, x.w, t.c)
+        g = plan.const(self.gamma.detach().float())
+        plan.launch("ydbl_channel_gate_add", x.struct(), t.struct(), g.data_ptr(), y.struct(), what="A2C2f.gamma",
+                    keep=[g])
+        return y
+
+
+class Upsample(PlanModule):
+    """nn.Upsample(size, scale_factor, mode) as a YAML layer ('nn.Upsample', [None, 2, "nearest"]): nearest x2 only,
+    ydbl_pool_up_concat's third segment."""
+
+    def __init__(self, size=None, scale_factor=None, mode="nearest"):
+        super().__init__()
+        if size is not None or scale_factor is None or float(scale_factor) != 2.0 or mode != "nearest":
+            raise NotImplementedError(f"Upsample(size={size}, scale_factor={scale_factor}, mode={mode!r}): only "
+                                      "scale_factor=2, mode='nearest' has a HIP path")
+        self.size, self.scale_factor, self.mode = size, scale_factor, mode
+
+    def forward(self, x):
+        if isinstance(x, torch.Tensor) and x.device.type in ("cpu", "meta"):
+            return nn.functional.interpolate(x, None, float(self.scale_factor), self.mode)
+        return run_module(self, x)
+
+    def emit(self, plan, x, out=None):
+        y = out if out is not None else plan.alloc(x.n, 2 * x.h, 2 * x.w, x.c)
+        plan.launch("ydbl_pool_up_concat", None, None, x.struct(), y.struct(), what="Upsample.nearest2")
+        return y
 
 
 class AdaHyperedgeGen(nn.Module):

@@ -13,6 +13,8 @@ input written in place into its slice of the concat buffer.
 
 from __future__ import annotations
 
+import ast
+import contextlib
 import json
 import math
 import os
@@ -34,11 +36,12 @@ REGISTRY: dict[str, type] = {
     c.__name__: c
     for c in (M.Conv, M.DWConv, M.DSConv, M.GhostConv, M.Concat, M.Bottleneck, M.C2f, M.C3, M.C3Ghost,
               M.GhostBottleneck, M.DSBottleneck, M.DSC3k, M.DSC3k2, M.HyperACE, M.DownsampleConv,
-              M.FullPAD_Tunnel, M.DySample, M.LSKblock, M.Detect)
+              M.FullPAD_Tunnel, M.DySample, M.LSKblock, M.Detect, M.AAttn, M.ABlock, M.A2C2f)
 }
+REGISTRY["nn.Upsample"] = M.Upsample  # the one torch.nn layer name the v13 YAMLs use (U/nn/tasks.py:972-973)
 _C1C2 = {"Conv", "DWConv", "GhostConv", "Bottleneck", "GhostBottleneck", "C2f", "C3", "C3Ghost", "DSC3k2", "DSConv",
-         "DSBottleneck"}
-_REPEAT_ARG = {"C2f", "C3", "C3Ghost", "DSC3k2"}
+         "DSBottleneck", "A2C2f"}
+_REPEAT_ARG = {"C2f", "C3", "C3Ghost", "DSC3k2", "A2C2f"}
 _C1_ONLY = {"DySample", "LSKblock"}
 
 
@@ -68,17 +71,22 @@ def guess_model_scale(model_path) -> str:
 def yaml_model_load(path) -> dict:
     """U/nn/tasks.py:1211-1224: 'yolov13n_DBL.yaml' -> unified 'yolov13_DBL' config with scale 'n'.
 
-    Built-in configs live in ydbl/cfg/models/*.json; an existing .yaml/.json path is read directly.
+    Built-in configs live in ydbl/cfg/models/*.json; an existing .yaml/.json path is read directly, and a scaled
+    name that does not exist beside an existing unified file ('yolov13n.yaml' next to 'yolov13.yaml') reads that.
     """
     path = Path(path)
     unified = re.sub(r"(\d+)([nslmx])(.+)?$", r"\1\3", path.stem)
-    if path.exists():
-        if path.suffix in (".yaml", ".yml"):
+    src = path
+    if not path.exists() and (path.parent / f"{unified}{path.suffix}").exists():
+        # 'yolov13n.yaml' next to a 'yolov13.yaml': the unified file at the scale of the name (U/nn/tasks.py:1216-1219)
+        src = path.parent / f"{unified}{path.suffix}"
+    if src.exists():
+        if src.suffix in (".yaml", ".yml"):
             import yaml
 
-            d = yaml.safe_load(path.read_text())
+            d = yaml.safe_load(src.read_text())
         else:
-            d = json.loads(path.read_text())
+            d = json.loads(src.read_text())
     else:
         for cand in (CFG_DIR / f"{unified}.json", CFG_DIR / f"{path.stem}.json"):
             if cand.exists():
@@ -109,6 +117,10 @@ def parse_model(d: dict, ch: int = 3, verbose: bool = False):
             raise KeyError(f"module '{name}' (layer {i}) has no MI355X implementation")
         m = REGISTRY[name]
         args = [nc if a == "nc" else a for a in args]
+        for j, a in enumerate(args):  # YAML delivers 'None' as a string (U/nn/tasks.py:1000-1003)
+            if isinstance(a, str):
+                with contextlib.suppress(ValueError, SyntaxError):
+                    args[j] = ast.literal_eval(a)
         n = n_ = max(round(n * depth), 1) if n > 1 else n
         if name in _C1C2:
             c1, c2 = ch[f], args[0]
@@ -120,6 +132,10 @@ def parse_model(d: dict, ch: int = 3, verbose: bool = False):
                 n = 1
             if name == "DSC3k2":
                 legacy = False
+            if name == "A2C2f":  # U/nn/tasks.py:1087-1091
+                legacy = False
+                if scale in "lx":
+                    args += [True, 1.5]
         elif name == "Concat":
             c2 = sum(ch[x] for x in f)
         elif name == "Detect":
@@ -390,8 +406,12 @@ def _propagate_shapes(layers, batch, h, w, ch):
         elif t in ("Bottleneck", "DSBottleneck"):
             cur = (batch, src[1], src[2], (m[-1] if isinstance(m, nn.Sequential) else m).cv2.conv.out_channels
                    if t == "Bottleneck" else (m[-1] if isinstance(m, nn.Sequential) else m).cv2.pw.out_channels)
-        elif t in ("C2f", "DSC3k2"):
+        elif t in ("C2f", "DSC3k2", "A2C2f"):
             cur = (batch, src[1], src[2], mm.cv2.conv.out_channels)
+        elif t in ("AAttn", "ABlock"):
+            cur = src
+        elif t == "nn.Upsample":
+            cur = (batch, 2 * src[1], 2 * src[2], src[3])
         elif t in ("C3", "C3Ghost"):
             cur = (batch, src[1], src[2], mm.cv3.conv.out_channels)
         elif t == "LSKblock":
