@@ -133,11 +133,38 @@ typedef struct {
   const float* dw_bias;
   int32_t dw_act;
   /* optional trailing 1x1 conv (Detect cls conv cv3[i][2], head.py:93-101) over y's 64 channels:
-   * tail_y[p][k] = sum_c tail_w[k][c] * y[p][c] + tail_b[k], k < tail_n <= 4 (y is still written) */
+   * tail_y[p][k] = sum_c tail_w[k][c] * y[p][c] + tail_b[k], k < tail_n <= 4 (y is still written, unless
+   * y_unused below) */
   const float* tail_w;
   const float* tail_b;
   ydbl_view tail_y;
   int32_t tail_n;
+  /* optional NMS-candidate sink of the tail (cand_count != NULL; f16 only): the launch is one Detect level's class
+   * branch (tail_n = nc) and appends that level's candidates to the lists of ydbl_decode_desc itself, exactly as
+   * ydbl_detect_decode would from tail_y and box: same filter (conf_thres, multi_label, classes), same scores
+   * (sigmoid of the stored f16 logit), same boxes, cand_idx = anchor (anchor * nc + cls when multi_label) with
+   * anchor = anchor0 + y * w + x.  box: the level's DFL logits [n,h,w,64] (f16, 16-byte aligned), written by an
+   * earlier launch of the stream and read only at pixels that hold a candidate.  level_stride: the level's stride.
+   * zero_counts != 0: cand_count[0..n) is zeroed by a kernel of this call ahead of the tiles -- set it on the first
+   * level's launch, clear it on the others, and the lists carry no state between calls.  Candidate order within an
+   * image is free (ydbl_nms sorts by (score, cand_idx)). */
+  float* cand_box;
+  float* cand_score;
+  int32_t* cand_cls;
+  int32_t* cand_idx;
+  int32_t* cand_count;
+  int32_t cand_cap;
+  float conf_thres;
+  int32_t multi_label;
+  int32_t nclasses;
+  const int32_t* classes;
+  float level_stride;
+  int32_t anchor0;
+  ydbl_view box;
+  int32_t zero_counts;
+  /* != 0 (tail only): nothing reads y, and the launch may leave it unwritten (the one-round-trip 64 -> 64 tile
+   * does; y's shape fields still describe the map, its pointer must still be valid) */
+  int32_t y_unused;
 } ydbl_dsconv_desc;
 int ydbl_dsconv_nhwc(const ydbl_dsconv_desc* d, void* stream);
 
@@ -310,7 +337,8 @@ int ydbl_hg_fused(const ydbl_hg_desc* d, void* stream);
  * Writes, when y_ref != NULL, the reference output layout y[n][4+nc][A] (xywh pixels, sigmoid).
  * Candidates per image (cap each): xyxy boxes, score, class, original flat index
  * (anchor for single-label, anchor*nc+cls for multi-label); cand_count[n] (int32) is
- * zeroed by this call.  classes/ncls: optional class filter. */
+ * zeroed by this call.  classes/ncls: optional class filter.  With y_ref == NULL the classes are evaluated first
+ * and a box is decoded (its 64 logits read) only where a candidate is offered: same candidates, bit for bit. */
 typedef struct {
   ydbl_view box[3], cls[3];
   int32_t nl, nc;

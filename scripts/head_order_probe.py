@@ -23,8 +23,9 @@ from ydbl.utils.synthetic import blob_images, load_trained  # noqa: E402
 
 def level_groups(steps):
     """Index ranges of the head's per-level launch groups: each level starts at a 'Detect.box3' launch or, for the
-    unfused P5 box branch, at the first of its two Conv3x3 launches; the head ends at the decode."""
-    dec = next(i for i, st in enumerate(steps) if st.what == "Detect.decode")
+    unfused P5 box branch, at the first of its two Conv3x3 launches; the head ends at the decode or, in a session
+    whose class-conv tails emit the candidates themselves (no decode launch), at the NMS."""
+    dec = next(i for i, st in enumerate(steps) if st.what in ("Detect.decode", "NMS"))
     first = next(i for i, st in enumerate(steps) if st.what == "Detect.box3")
     starts = [i for i in range(first, dec) if steps[i].what == "Detect.box3"]
     # the P5 level: after the last box3 group's three launches
@@ -51,7 +52,22 @@ def main():
     rev = p1.steps[:first] + [st for a, b in reversed(groups) for st in p1.steps[a:b]] + p1.steps[dec:]
     assert len(rev) == len(p1.steps)
 
-    def capture(steps1):
+    def tails(a, b):
+        return [st.args[0] for st in p1.steps[a:b] if st.fn.__name__ == "ydbl_dsconv_nhwc" and st.args[0].cand_count]
+
+    def zero_first(order):
+        """The candidate counters are zeroed by the first level group that runs (the launch copies the flag)."""
+        for k, (a, b) in enumerate(order):
+            for d in tails(a, b):
+                d.zero_counts = int(k == 0)
+
+    def capture(steps1, order=None):
+        zero_first(order or groups)
+        g = _capture(steps1)
+        zero_first(groups)
+        return g
+
+    def _capture(steps1):
         side = torch.cuda.Stream(dev)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
@@ -64,7 +80,7 @@ def main():
         torch.cuda.synchronize(dev)
         return g
 
-    g_same, g_rev = capture(p1.steps), capture(rev)
+    g_same, g_rev = capture(p1.steps), capture(rev, list(reversed(groups)))
     g_rev.replay()
     torch.cuda.synchronize(dev)
     assert torch.equal(sess.det, ref[0]) and torch.equal(sess.count, ref[1]), "reordered head changed the output"

@@ -2,6 +2,7 @@
 // MFMA k-chunk (f16 16x16x32 / exact f32 4x 16x16x4) and the fused epilogue.
 #pragma once
 #include "common.hpp"
+#include "decode_math.hpp"
 
 namespace ydbl {
 
@@ -26,6 +27,12 @@ struct ConvArgs {
   // y3[p][k] = sum_c t3w[k][c] * T(y[p][c]) + t3b[k]
   const float* t3w; const float* t3b;
   T* y3; int y3cs; int nt3;
+  // optional NMS-candidate sink of that tail (sk.ccount != nullptr; fp16, nt3 = the class count): the launch is one
+  // Detect level's class branch and appends the level's candidates itself (tail_store below).  skbox: the
+  // level's 64 box logits per pixel, ska0: the level's first anchor, skstride: its stride
+  CandSink sk;
+  const T* skbox; int skboxcs; int ska0; float skstride;
+  int y_off;  // the tail launch leaves y unwritten (nothing reads it)
   // split-K (conv_wsk_kernel): ksplit > 1 -> fp32 partial tiles ws[z][P][round_up(Cout, 4)], summed + epilogue by
   // splitk_epilogue_kernel
   float* ws; int64_t ws_bytes; int ksplit;
@@ -276,12 +283,41 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs<T>& p, const f32x4 
   }
 }
 
+// Stores one pixel's class logits (part: the four lane groups' sums, equal on the pixel's four lanes g = 0..3)
+// and, with a candidate sink, offers the pixel as an anchor: the four lanes are the decode's quad (lane g = side g
+// and class g), the logits are taken as stored (the decode reads the fp16 values), and the level's box launch has
+// run before this one, so a quad that holds a candidate reads its 64 box logits from the level buffer.
+template <typename T, bool SINK>
+__device__ __forceinline__ void tail_store(const ConvArgs<T>& p, const float (&part)[4], int64_t pix, bool ok, int g) {
+  T lv[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) lv[k] = T(part[k] + (k < p.nt3 ? p.t3b[k] : 0.f));
+  if (g == 0 && ok) {
+    T* o = p.y3 + pix * p.y3cs;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (k < p.nt3) o[k] = lv[k];
+  }
+  if constexpr (SINK && sizeof(T) == 2) {
+    if (p.sk.ccount) {  // uniform
+      const int hw = p.Ho * p.Wo;
+      const int b = (int)pix / hw, loc = (int)pix - b * hw;
+      const int gy = loc / p.Wo, gx = loc - gy * p.Wo;
+      auto logit = [&](int j) { return float(j == 0 ? lv[0] : j == 1 ? lv[1] : j == 2 ? lv[2] : lv[3]); };
+      quad_candidates<T, 16>(p.sk, b, g, ok, p.nt3, logit, p.skbox + pix * p.skboxcs, gx, gy, p.skstride,
+                             p.ska0 + loc);
+    }
+  }
+}
+
 // Trailing 1x1 conv with <= 4 outputs over all Cout channels of a pixel, for kernels whose wave holds
 // every channel of its pixels (TN * 16 == Cout): the Detect head's class conv cv3[i][2] (head.py:93-101)
 // after its DWConv -> Conv1x1 pair.  Lane (r16, g) holds channels co[i]..co[i]+3 of pixel pp[j]; the
 // rounded activations (T, as the unfused path stores them) are dotted with the weights per lane and the
 // four lane groups are summed by xor-shuffles (fixed order); lane group 0 stores.
-template <typename T, int TN, int TM>
+// SINK: the instance also serves a candidate sink (tail_store); the others are the plain tail, instruction for
+// instruction.
+template <typename T, int TN, int TM, bool SINK = false>
 __device__ __forceinline__ void conv_tail_1x1(const ConvArgs<T>& p, const f32x4 (&acc)[TN][TM], const int64_t (&pp)[TM],
                                               const bool (&pv)[TM], const int (&co)[TN], int g) {
   float bv[TN][4], wv[TN][4][4];
@@ -309,10 +345,7 @@ __device__ __forceinline__ void conv_tail_1x1(const ConvArgs<T>& p, const f32x4 
       part[k] += __shfl_xor(part[k], 16);
       part[k] += __shfl_xor(part[k], 32);
     }
-    if (g == 0 && pv[j]) {
-      T* o = p.y3 + pp[j] * p.y3cs;
-      for (int k = 0; k < p.nt3; ++k) o[k] = T(part[k] + p.t3b[k]);
-    }
+    tail_store<T, SINK>(p, part, pp[j], pv[j], g);
   }
 }
 
@@ -320,7 +353,7 @@ __device__ __forceinline__ void conv_tail_1x1(const ConvArgs<T>& p, const f32x4 
 // recomputed.  Lanes of one pixel share pv, so the xor-shuffles only mix lanes of the same pixel.
 // s_t: the weights [4][Cout] staged in LDS (rows past nt3 zero), or nullptr to read them from global memory (a
 // late round trip of 16 x nt3 scalar loads per lane at the very end of the launch: kbench pair 64+tail @80^2 bs16 24.8 vs 20.5 us, profiles/r05/r05_bias_lds_ab.txt).
-template <typename T, int TN, int TM>
+template <typename T, int TN, int TM, bool SINK = false>
 __device__ __forceinline__ void conv_tail_1x1_vals(const ConvArgs<T>& p, const float (&ys)[TN][TM][4],
                                                    const int64_t (&pp)[TM], const bool (&pv)[TM], const int (&co)[TN],
                                                    int g, const float* s_t = nullptr) {
@@ -356,10 +389,7 @@ __device__ __forceinline__ void conv_tail_1x1_vals(const ConvArgs<T>& p, const f
       part[k] += __shfl_xor(part[k], 16);
       part[k] += __shfl_xor(part[k], 32);
     }
-    if (g == 0 && pv[j]) {
-      T* o = p.y3 + pp[j] * p.y3cs;
-      for (int k = 0; k < p.nt3; ++k) o[k] = T(part[k] + p.t3b[k]);
-    }
+    tail_store<T, SINK>(p, part, pp[j], pv[j], g);
   }
 }
 

@@ -19,6 +19,7 @@
 #include <cmath>
 
 #include "common.hpp"
+#include "decode_math.hpp"
 
 extern "C" __device__ unsigned long long __ockl_wfred_or_u64(unsigned long long);  // DPP wave OR (ockl)
 
@@ -32,40 +33,20 @@ struct DecodeArgs {
   int nl, nc, A;
   int a_end[3];
   float stride[3];
-  float conf;
-  int multi;
-  const int* classes; int ncls;
   float* yref;
-  float* cbox; float* cscore; int* ccls; int* cidx; int* ccount;
-  int cap;
+  CandSink k;  // candidate lists and filter (decode_math.hpp, with the per-anchor arithmetic)
 };
-
-// Slot of this lane's candidate in image b's list: one atomic per wave (the first active lane adds the
-// wave's candidate count, the others take their rank among the active lanes).  Candidates cluster on
-// objects, so a wave often holds tens of them; per-lane atomics on the one counter serialize in L2.
-__device__ __forceinline__ int wave_slot(int* counter, bool want) {
-  const uint64_t m = __ballot(want);
-  if (!want) return -1;
-  const int lane = threadIdx.x & 63;
-  const int leader = __ffsll((long long)m) - 1;
-  int base = 0;
-  if (lane == leader) base = atomicAdd(counter, __popcll(m));
-  base = __shfl(base, leader);
-  return base + __popcll(m & ((1ull << lane) - 1));
-}
-
-__device__ __forceinline__ bool class_ok(int j, const int* classes, int ncls) {
-  if (!classes) return true;
-  for (int q = 0; q < ncls; ++q)
-    if (classes[q] == j) return true;
-  return false;
-}
 
 // Four lanes per anchor (a quad): lane s computes side s's DFL expectation (16 bins; the quad's four sides are
 // then shared by shuffles) and the classes j = s, s + 4, ...; so a lane's dependent chain is 16 exponentials
 // instead of 64, and the launch has four times the waves to hide it.  Same arithmetic per value as one lane per
 // anchor: the decoded boxes, scores and candidate sets are unchanged (candidate order within an image may differ;
 // every candidate carries its anchor / class index).
+//
+// Without y_ref (the session path: only the candidates are wanted) the classes come first and the box is decoded
+// only in quads that hold a candidate (quad_candidates, decode_math.hpp): same values, same candidate sets, and
+// the 64 box logits of the other anchors are never read.  With y_ref every anchor's box is written, so it is
+// decoded first, as below.
 //
 // AUG: one pass of test-time augmentation (include/ydbl.h ydbl_decode_aug).  Anchors outside the pass's window
 // leave at once (whole quads); the others de-scale and de-flip xywh, and land at their position of the merged
@@ -91,91 +72,52 @@ __device__ __forceinline__ void decode_body(const DecodeArgs<T>& p, const AugArg
   const DView<const T>& bx = p.box[l];
   const int gx = loc % bx.w, gy = loc / bx.w;
   const T* bp = bx.at(b, gy, gx);
-  float mine;
-  {  // DFL: softmax over 16 bins, expectation with weights 0..15
-    float v[16];
-    load_f<8>(bp + s * 16, v);
-    load_f<8>(bp + s * 16 + 8, v + 8);
-    float m = v[0];
-#pragma unroll
-    for (int k = 1; k < 16; ++k) m = fmaxf(m, v[k]);
-    float e[16], sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      e[k] = expf(v[k] - m);
-      sum += e[k];
+  const T* cp = p.cls[l].at(b, gy, gx);
+  const CandSink& k = p.k;
+  if constexpr (!AUG) {
+    if (!p.yref) {
+      quad_candidates<T, 1>(k, b, s, true, p.nc, [&](int j) { return float(cp[j]); }, bp, gx, gy, p.stride[l], a);
+      return;
     }
-    // softmax weights as e * (1 / sum): one division per side instead of 16 (<= 1 ulp per weight, far
-    // inside the decode tolerance; the reference's DFL conv sums the 16 products in its own order anyway)
-    const float inv = 1.0f / sum;
-    float acc = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) acc += float(k) * (e[k] * inv);
-    mine = acc;
   }
+  const float mine = dfl_side(bp + s * 16);
   const int q0 = (threadIdx.x & 63) & ~3;  // the quad's first lane
   float dist[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) dist[k] = __shfl(mine, q0 + k);
-  const float ax = float(gx) + 0.5f, ay = float(gy) + 0.5f, st = p.stride[l];
-  const float x1 = ax - dist[0], y1 = ay - dist[1], x2 = ax + dist[2], y2 = ay + dist[3];
-  float cx = ((x1 + x2) / 2.0f) * st, cy = ((y1 + y2) / 2.0f) * st;
-  float w = (x2 - x1) * st, h = (y2 - y1) * st;
+  for (int i = 0; i < 4; ++i) dist[i] = __shfl(mine, q0 + i);
+  Xywh v = dist2xywh(gx, gy, dist, p.stride[l]);
   int64_t A = p.A;
   int pos = a;  // the anchor's column of y_ref and its candidate index
   if constexpr (AUG) {
     // _descale_pred (U/nn/tasks.py:378-387): p[:, :4] /= scale, an IEEE division, then x = img_w - x
-    cx = __fdiv_rn(cx, g.scale); cy = __fdiv_rn(cy, g.scale); w = __fdiv_rn(w, g.scale); h = __fdiv_rn(h, g.scale);
-    if (g.flip_w != 0.f) cx = g.flip_w - cx;
+    v.cx = __fdiv_rn(v.cx, g.scale); v.cy = __fdiv_rn(v.cy, g.scale);
+    v.w = __fdiv_rn(v.w, g.scale); v.h = __fdiv_rn(v.h, g.scale);
+    if (g.flip_w != 0.f) v.cx = g.flip_w - v.cx;
     A = g.ystride;
     pos = g.pos_base + (a - g.a_lo);
   }
   if (p.yref) {
     float* yr = p.yref + (int64_t)b * (4 + p.nc) * A + pos;
-    yr[s * A] = s == 0 ? cx : s == 1 ? cy : s == 2 ? w : h;
+    yr[s * A] = s == 0 ? v.cx : s == 1 ? v.cy : s == 2 ? v.w : v.h;
   }
-  // xywh2xyxy (U/utils/ops.py:416-433)
-  const float hw = w / 2.0f, hh = h / 2.0f;
-  const float bx1 = cx - hw, by1 = cy - hh, bx2 = cx + hw, by2 = cy + hh;
-  const T* cp = p.cls[l].at(b, gy, gx);
+  const f32x4 box = xywh2xyxy(v);
   float best = -1.f;
   int bj = 0;
   for (int j = s; j < p.nc; j += 4) {
-    const float sc = 1.0f / (1.0f + expf(-float(cp[j])));
+    const float sc = cls_score(float(cp[j]));
     if (p.yref) p.yref[((int64_t)b * (4 + p.nc) + 4 + j) * A + pos] = sc;
-    if (p.multi) {
-      const int slot = wave_slot(p.ccount + b, sc > p.conf && class_ok(j, p.classes, p.ncls));
-      if (slot >= 0) {
-        if (slot < p.cap) {
-          const int64_t o = (int64_t)b * p.cap + slot;
-          *reinterpret_cast<f32x4*>(p.cbox + o * 4) = f32x4{bx1, by1, bx2, by2};
-          p.cscore[o] = sc; p.ccls[o] = j; p.cidx[o] = pos * p.nc + j;
-        }
-      }
+    if (k.multi) {
+      const int slot = wave_slot(k.ccount + b, sc > k.conf && class_ok(j, k.classes, k.ncls));
+      cand_write(k, b, slot, box, sc, j, pos * p.nc + j);
     } else if (sc > best) {  // torch.max: first index of the maximum (within this lane's classes)
       best = sc;
       bj = j;
     }
   }
-  if (p.multi) return;
-  // the quad's first maximum: larger score, or the same score at a smaller class index
-#pragma unroll
-  for (int k = 1; k < 4; k <<= 1) {
-    const float ob = __shfl_xor(best, k);
-    const int oj = __shfl_xor(bj, k);
-    if (ob > best || (ob == best && oj < bj)) {
-      best = ob;
-      bj = oj;
-    }
-  }
-  const int slot = wave_slot(p.ccount + b, s == 0 && best > p.conf && class_ok(bj, p.classes, p.ncls));
-  if (slot >= 0) {
-    if (slot < p.cap) {
-      const int64_t o = (int64_t)b * p.cap + slot;
-      *reinterpret_cast<f32x4*>(p.cbox + o * 4) = f32x4{bx1, by1, bx2, by2};
-      p.cscore[o] = best; p.ccls[o] = bj; p.cidx[o] = pos;
-    }
-  }
+  if (k.multi) return;
+  quad_first_max<1>(best, bj);
+  const int slot = wave_slot(k.ccount + b, s == 0 && best > k.conf && class_ok(bj, k.classes, k.ncls));
+  cand_write(k, b, slot, box, best, bj, pos);
 }
 
 template <typename T>
@@ -1276,11 +1218,9 @@ static int decode_t(const ydbl_decode_desc* d, const ydbl_decode_aug* g, hipStre
     a.stride[l] = d->stride[l];
   }
   a.nl = d->nl; a.nc = d->nc; a.A = A;
-  a.conf = d->conf_thres; a.multi = d->multi_label;
-  a.classes = d->classes; a.ncls = d->nclasses;
   a.yref = d->y_ref;
-  a.cbox = d->cand_box; a.cscore = d->cand_score; a.ccls = d->cand_cls; a.cidx = d->cand_idx; a.ccount = d->cand_count;
-  a.cap = d->cap;
+  a.k = CandSink{d->cand_box, d->cand_score, d->cand_cls, d->cand_idx, d->cand_count, d->cap,
+                 d->conf_thres, d->multi_label, d->classes, d->nclasses};
   const int B = d->box[0].n;
   const dim3 grid((unsigned)cdiv((int64_t)A * 4, 256), B);  // a quad per anchor
   if (!g) {

@@ -71,7 +71,8 @@ bool try_dsc_lean(const ConvArgs<_Float16>& a, const float* dww, const float* dw
   if ((off && *off == '0') || dil != 1 || a.y2) return false;
   if (a.xcs % 8 || a.ycs % 4 || (a.res && a.rcs % 4) || a.KPAD != a.Cin) return false;
   const int c = a.Cin, co = a.Cout;
-  if (a.t3w && co != 64) return false;
+  // the class-conv tail: only the tiles whose waves hold all 64 output channels compute it (dsc_lean.hpp, TN == 4)
+  if (a.t3w && (co != 64 || c > 128)) return false;
   // 128+ input channels only while the map is small enough that the chunked kernel cannot fill the chip
   // (<= 160 8x8 tiles: DBL-n's 20^2 maps at bs16).  On DBL-s bs64 (800 tiles at 40^2) and DBL-l 1280
   // (400 tiles at 80^2) the lean kernel's 512-thread one-round-trip tiles lost to the chunked kernel:

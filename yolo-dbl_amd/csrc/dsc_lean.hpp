@@ -306,7 +306,7 @@ __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const flo
 #pragma unroll
             for (int q = 0; q < 4; ++q) v[q] = float(rv[i][j][q]) * v[q];
           }
-          st8(p.y, pp[j] * p.ycs + co[i], v);
+          if (!(TAIL && p.y_off)) st8(p.y, pp[j] * p.ycs + co[i], v);  // (uniform) the tail's y may have no reader
           if constexpr (TAIL) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) ys[i][j][q] = round_to<T>(v[q]);
@@ -326,7 +326,7 @@ __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const flo
       epilogue(ActC<ACT_RT>{}, ActC<-1>{});
     }
     if constexpr (TAIL && NCG == 1 && TN == 4) {  // Detect class conv over the 64 output channels (CO == 64)
-      conv_tail_1x1_vals<T, TN, TM>(p, ys, pp, pv, co, g, reinterpret_cast<const float*>(smem + L::T));
+      conv_tail_1x1_vals<T, TN, TM, true>(p, ys, pp, pv, co, g, reinterpret_cast<const float*>(smem + L::T));
     }
   }
 }

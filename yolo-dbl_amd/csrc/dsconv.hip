@@ -30,7 +30,9 @@ __device__ __forceinline__ void store4(float* d, const float* a) {
   *reinterpret_cast<f32x4*>(d) = f32x4{a[0], a[1], a[2], a[3]};
 }
 
-template <typename T, int K, int S, int DIL, int TH, int TW, int CSEG, int NTN, bool DBUF>
+// SINK: the class-conv tail also emits the NMS candidates (conv_common.hpp, tail_store): an instance of its own,
+// built for the Detect pair's shape only (fp16, k3 s1, 64 outputs), so that every other launch runs the plain code.
+template <typename T, int K, int S, int DIL, int TH, int TW, int CSEG, int NTN, bool DBUF, bool SINK = false>
 __global__ __launch_bounds__(256, 2) void dsconv_kernel(ConvArgs<T> p, const float* __restrict__ dww,
                                                         const float* __restrict__ dwb, int dw_act, int tiles_x,
                                                         int tiles_y, int co_splits) {
@@ -217,7 +219,7 @@ __global__ __launch_bounds__(256, 2) void dsconv_kernel(ConvArgs<T> p, const flo
   // VGPRs, a wave per SIMD on the k5 / k7 tiles and 20 bytes of scratch on the stride-2 ones
   conv_epilogue<T, NTN, TMW, false, ACT_RT>(p, acc, pp, pv, co, s_bias, co0);
   if constexpr (NTN == 4) {  // the tail is only launched with Cout 64 = NTN * 16 (host-checked)
-    if (p.t3w) conv_tail_1x1<T, NTN, TMW>(p, acc, pp, pv, co, g);
+    if (p.t3w) conv_tail_1x1<T, NTN, TMW, SINK>(p, acc, pp, pv, co, g);
   }
 }
 
@@ -229,6 +231,9 @@ static void launch_ds_tile(const ConvArgs<T>& a, const float* dww, const float* 
     const int cs = (int)cdiv(a.Cout, ntn * 16);
     kern<<<(unsigned)(ntiles * cs), 256, 0, s>>>(a, dww, dwb, dw_act, tiles_x, tiles_y, cs);
   };
+  if constexpr (sizeof(T) == 2 && K == 3 && S == 1 && DIL == 1) {
+    if (a.sk.ccount) return go(dsconv_kernel<T, K, S, DIL, TH, TW, CSEG, 4, DBUF, true>, 4);  // (Cout 64: ds_check)
+  }
   if (a.Cout <= 32) go(dsconv_kernel<T, K, S, DIL, TH, TW, CSEG, 2, DBUF>, 2);
   // k3 s1 with < 512 tiles: two 64-channel column workgroups per tile (the cheap depthwise phase is
   // recomputed; 128->128 @20^2 bs32 15.0 -> 11.8 us; k7 loses: 19.7 -> 25.4)
@@ -272,6 +277,13 @@ static ConvArgs<T> ds_args(const ydbl_dsconv_desc* d) {
   if (d->tail_w) {
     a.t3w = d->tail_w; a.t3b = d->tail_b; a.nt3 = d->tail_n;
     a.y3 = reinterpret_cast<T*>(d->tail_y.ptr); a.y3cs = d->tail_y.cs;
+    a.y_off = d->y_unused;
+    if (d->cand_count) {
+      a.sk = CandSink{d->cand_box, d->cand_score, d->cand_cls, d->cand_idx, d->cand_count, d->cand_cap,
+                      d->conf_thres, d->multi_label, d->classes, d->nclasses};
+      a.skbox = reinterpret_cast<const T*>(d->box.ptr); a.skboxcs = d->box.cs;
+      a.ska0 = d->anchor0; a.skstride = d->level_stride;
+    }
   }
   a.P = d->y.n * d->y.h * d->y.w;
   return a;
@@ -314,7 +326,24 @@ int ds_check(const ydbl_dsconv_desc* d) {
         d->tail_y.n != d->y.n || d->tail_y.h != d->y.h || d->tail_y.w != d->y.w)
       return fail(YDBL_EINVAL, "dsconv: tail needs y.c 64, 1 <= tail_n <= 4, tail_y [n,h,w,tail_n] of y's dtype, no residual");
   }
+  if (d->y_unused && !d->tail_w) return fail(YDBL_EINVAL, "dsconv: y_unused needs the tail (its output is the launch's result)");
+  if (d->cand_count) {
+    if (!d->tail_w || d->y.dtype != YDBL_F16 || !d->cand_box || !d->cand_score || !d->cand_cls || !d->cand_idx ||
+        d->cand_cap < 1 || d->anchor0 < 0 || (d->nclasses > 0 && !d->classes) || d->k != 3 || d->stride != 1 ||
+        d->dil != 1)
+      return fail(YDBL_EINVAL, "dsconv: the candidate sink needs the tail, fp16, k 3 / stride 1 / dil 1 (the Detect "
+                               "pair) and all five candidate arrays");
+    if (check_view(&d->box, "dsconv.box", true) || d->box.c != 64 || d->box.dtype != YDBL_F16 || d->box.n != d->y.n ||
+        d->box.h != d->y.h || d->box.w != d->y.w)
+      return fail(YDBL_EINVAL, "dsconv: the sink's box view must be fp16 [n,h,w,64] of y's map, 16-byte aligned");
+  }
   return YDBL_OK;
+}
+
+// Zeroes the candidate counters ahead of the first level's tile kernel (a kernel, not hipMemsetAsync: detect.hip,
+// zero_counts_kernel, records why).
+__global__ void ds_zero_counts_kernel(int* c, int n) {
+  for (int i = threadIdx.x; i < n; i += blockDim.x) c[i] = 0;
 }
 
 }  // namespace ydbl
@@ -324,5 +353,6 @@ using namespace ydbl;
 extern "C" int ydbl_dsconv_nhwc(const ydbl_dsconv_desc* d, void* stream) {
   if (const int rc = ds_check(d)) return rc;
   const hipStream_t s = as_stream(stream);
+  if (d->cand_count && d->zero_counts) ds_zero_counts_kernel<<<1, 256, 0, s>>>(d->cand_count, d->y.n);
   return d->x.dtype == YDBL_F16 ? run_ds<_Float16>(d, s) : run_ds<float>(d, s);
 }

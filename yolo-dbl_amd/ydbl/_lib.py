@@ -45,7 +45,13 @@ class DsConvDesc(C.Structure):
                 ("bias", C.c_void_p), ("k", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32),
                 ("dil", C.c_int32), ("kpad", C.c_int32), ("act", C.c_int32), ("res_mode", C.c_int32),
                 ("dw_bias", C.c_void_p), ("dw_act", C.c_int32), ("tail_w", C.c_void_p), ("tail_b", C.c_void_p),
-                ("tail_y", View), ("tail_n", C.c_int32)]
+                ("tail_y", View), ("tail_n", C.c_int32),
+                # the tail's NMS-candidate sink (include/ydbl.h): unset (cand_count NULL) unless a session fills it
+                ("cand_box", C.c_void_p), ("cand_score", C.c_void_p), ("cand_cls", C.c_void_p),
+                ("cand_idx", C.c_void_p), ("cand_count", C.c_void_p), ("cand_cap", C.c_int32),
+                ("conf_thres", C.c_float), ("multi_label", C.c_int32), ("nclasses", C.c_int32),
+                ("classes", C.c_void_p), ("level_stride", C.c_float), ("anchor0", C.c_int32), ("box", View),
+                ("zero_counts", C.c_int32), ("y_unused", C.c_int32)]
     g2_w = g0_w = None  # not in the ABI: bench.py's roofline still asks every DSConv descriptor for these two
 
 

@@ -169,7 +169,11 @@ class DetectSession:
                         self.pred.data_ptr() if self.pred is not None else None,
                         self.cand_box.data_ptr(), self.cand_score.data_ptr(), self.cand_cls.data_ptr(),
                         self.cand_idx.data_ptr(), self.cand_count.data_ptr(), cap)
-        plan.launch("ydbl_detect_decode", dd, what="Detect.decode", keep=[dd])
+        # No decode pass when every level's class conv is the tail of a DWConv -> Conv1x1 launch (DBL-n, nc <= 4,
+        # fp16) and no prediction tensor is wanted: those launches emit the candidates themselves (_fuse_candidates)
+        self.fused_candidates = self.pred is None and self._fuse_candidates(plan, cm.levels, dd)
+        if not self.fused_candidates:
+            plan.launch("ydbl_detect_decode", dd, what="Detect.decode", keep=[dd])
         nd = NmsDesc(self.cand_box.data_ptr(), self.cand_score.data_ptr(), self.cand_cls.data_ptr(),
                      self.cand_idx.data_ptr(), self.cand_count.data_ptr(), batch, cap, self.iou, self.max_det,
                      int(max_nms), int(bool(agnostic)), float(max_wh), float(w) if clip else 0.0,
@@ -183,6 +187,32 @@ class DetectSession:
         self._graph = None
         if hasattr(self, "bind_ptrs"):
             self._init_slots()
+
+    @staticmethod
+    def _fuse_candidates(plan: Plan, levels, dd: DecodeDesc) -> bool:
+        """Point the candidate sinks of the plan's class-conv tail launches (include/ydbl.h, ydbl_dsconv_desc) at the
+        decode descriptor's lists.  Only when the plan is fp16 and EVERY level's class logits are written by such a
+        tail (in level order, after the level's box launch: Detect.emit); else nothing is touched and the caller
+        keeps the decode launch.  The first level's launch zeroes the counters."""
+        if plan.dtype != torch.float16:
+            return False
+        tails = {}
+        for st in plan.steps:
+            if st.fn.__name__ == "ydbl_dsconv_nhwc" and st.args[0].tail_w:
+                tails[st.args[0].tail_y.ptr] = st.args[0]
+        descs = [tails.get(dd.cls[i].ptr) for i in range(len(levels))]
+        if any(d is None for d in descs):
+            return False
+        a0 = 0
+        for i, (lv, d) in enumerate(zip(levels, descs)):
+            d.cand_box, d.cand_score, d.cand_cls = dd.cand_box, dd.cand_score, dd.cand_cls
+            d.cand_idx, d.cand_count, d.cand_cap = dd.cand_idx, dd.cand_count, dd.cap
+            d.conf_thres, d.multi_label = dd.conf_thres, dd.multi_label
+            d.classes, d.nclasses = dd.classes, dd.nclasses
+            d.level_stride, d.anchor0, d.box = dd.stride[i], a0, dd.box[i]
+            d.zero_counts = int(i == 0)
+            a0 += lv.h * lv.w
+        return True
 
     def _init_split(self, model, batch, h, w, dtype, conf, iou, max_det, multi_label, agnostic, classes, max_nms,
                     max_wh, clip, keep_pred, use_graph, device, fp8, streams, nms, outputs):

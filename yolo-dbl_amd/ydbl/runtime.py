@@ -255,9 +255,13 @@ class Plan:
         """Per-launch time as the kernels run inside the step's hipGraph: every launch captured `reps`
         times back to back into a graph of its own, replayed `iters` times between a HIP event pair on
         the replaying stream; min replay time / reps.  Unlike run_timed this carries no per-launch host
-        or event overhead, so it agrees with rocprofv3's kernel durations (bench.py's roofline)."""
+        or event overhead, so it agrees with rocprofv3's kernel durations (bench.py's roofline).  A launch that
+        appends to a list (the class-conv tails that emit NMS candidates: only the first level's zeroes the counters)
+        piles its repeats up, so the whole plan runs once before every capture: each step is timed on the buffers a
+        real step hands it."""
         out = []
         for st in self.steps:
+            self.run()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 s = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
