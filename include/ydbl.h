@@ -165,6 +165,20 @@ typedef struct {
   /* != 0 (tail only): nothing reads y, and the launch may leave it unwritten (the one-round-trip 64 -> 64 tile
    * does; y's shape fields still describe the map, its pointer must still be valid) */
   int32_t y_unused;
+  /* optional deferred mode of the sink (tile_mask != NULL; needs cand_count): the level's box launch runs AFTER this
+   * one, as ydbl_bottleneck_nhwc with the same tile_mask and a candidate sink, and computes box logits only where a
+   * candidate is.  This launch filters, scores and takes slots exactly as above and writes cand_score, cand_cls and
+   * cand_idx; it does not read box (the view is ignored) and does not write cand_box.  Instead it stores 1 into the
+   * mask byte of each candidate's tile: tile_mask[(img * mask_tiles_img) + (y / 8) * mask_tiles_x + x / 16] -- the
+   * mask granularity is the box kernel's tile, 8 rows x 16 columns, so mask_tiles_x = ceil(w / 16) and
+   * mask_tiles_img = mask_tiles_x * ceil(h / 8) (checked).  mask_zero / mask_zero_bytes: one contiguous buffer holding
+   * the masks of every deferred level of the head; the call that has zero_counts set zeroes it in the same kernel as
+   * the counters (it need not have a tile_mask of its own), so no mask state is carried between calls. */
+  uint8_t* tile_mask;
+  int32_t mask_tiles_x;
+  int32_t mask_tiles_img;
+  uint8_t* mask_zero;
+  int32_t mask_zero_bytes;
 } ydbl_dsconv_desc;
 int ydbl_dsconv_nhwc(const ydbl_dsconv_desc* d, void* stream);
 
@@ -460,6 +474,23 @@ typedef struct {
   const void* params;
   int32_t c_mid;     /* intermediate channels: 0 = c/2 (Bottleneck e=0.5); 64 with c = 64 (Detect box branch) */
   int32_t pw;        /* 1: params from ydbl_detect_box_pack, y = conv1x1(cv2 output) + b3 (c = c_mid = 64) */
+  /* optional sparse box launch (pw = 1 and 8-row tiles only, else YDBL_EINVAL).  tile_mask != NULL: one byte per
+   * 8-row x 16-column tile, [n][ceil(h / 8)][ceil(w / 16)] (the deferred class tail of ydbl_dsconv_desc writes it); a
+   * workgroup whose byte is 0 returns before it loads anything and leaves its part of y unwritten, the others compute
+   * and store their tile exactly as the unmasked launch does.  cand_count != NULL (needs tile_mask): the candidate
+   * sink -- after storing its tile a workgroup scans cand_idx[img][0 .. min(cand_count[img], cand_cap)), and for each
+   * entry whose anchor (cand_idx, or cand_idx / nc when multi_label) lies in this level (anchor0 .. anchor0 + h*w) and
+   * in its tile, decodes the box from the 64 logits as stored in f16 (DFL, dist2bbox, xywh2xyxy, level_stride: the
+   * arithmetic of ydbl_detect_decode, bit for bit) into cand_box[img][slot].  1 <= nc <= 4. */
+  const uint8_t* tile_mask;
+  float* cand_box;
+  const int32_t* cand_idx;
+  const int32_t* cand_count;
+  int32_t cand_cap;
+  float level_stride;
+  int32_t anchor0;
+  int32_t nc;
+  int32_t multi_label;
 } ydbl_bottleneck_desc;
 int64_t ydbl_bottleneck_params_size(int32_t c);
 int ydbl_bottleneck_pack(const float* w1, const float* b1, const float* w2, const float* b2, int32_t c, void* out);

@@ -29,7 +29,11 @@ struct ConvArgs {
   T* y3; int y3cs; int nt3;
   // optional NMS-candidate sink of that tail (sk.ccount != nullptr; fp16, nt3 = the class count): the launch is one
   // Detect level's class branch and appends the level's candidates itself (tail_store below).  skbox: the
-  // level's 64 box logits per pixel, ska0: the level's first anchor, skstride: its stride
+  // level's 64 box logits per pixel, ska0: the level's first anchor, skstride: its stride.
+  // The sink's deferred mode (sk.cbox == nullptr; instances of their own, SINK_DEFER) reads no box and writes no
+  // cand_box, and flags the candidates' 8 x 16 tiles instead (include/ydbl.h): there skbox is the tile mask's bytes
+  // [N][ceil(Ho / 8)][skboxcs] and skboxcs the tiles per row -- no field of its own, since this block is an argument of
+  // every convolution kernel and a longer one changes the code of all of them.
   CandSink sk;
   const T* skbox; int skboxcs; int ska0; float skstride;
   int y_off;  // the tail launch leaves y unwritten (nothing reads it)
@@ -37,7 +41,25 @@ struct ConvArgs {
   // splitk_epilogue_kernel
   float* ws; int64_t ws_bytes; int ksplit;
   int epi_generic;  // YDBL_EPI_GENERIC=1: every epilogue takes its runtime-dispatch form (common.hpp, with_act)
+
+  // The deferred sink's view of the box fields.  Only these three functions know the double use: sk_defer() sets it
+  // up, the launchers ask sk_deferred() and hand such arguments to SINK_DEFER instances only (anything else is
+  // refused: launch_ds_tile, try_dsc_lean), and those instances read the mask through sk_mask().
+  void sk_defer(unsigned char* mask, int tiles_x) {
+    sk.cbox = nullptr;
+    skbox = reinterpret_cast<const T*>(mask);
+    skboxcs = tiles_x;
+  }
+  __host__ __device__ bool sk_deferred() const { return sk.ccount != nullptr && sk.cbox == nullptr; }
+  // the mask byte of pixel (gy, gx) of image b: tiles of 8 rows x 16 columns, skboxcs per row
+  __device__ __forceinline__ unsigned char* sk_mask(int b, int gy, int gx) const {
+    unsigned char* m = reinterpret_cast<unsigned char*>(const_cast<T*>(skbox));
+    return m + ((int64_t)b * ((Ho + 7) >> 3) + (gy >> 3)) * skboxcs + (gx >> 4);
+  }
 };
+
+// the candidate sink a tail instance is compiled for
+constexpr int SINK_NONE = 0, SINK_BOX = 1, SINK_DEFER = 2;
 
 // ---- operand policy: f16/f32 vectors, or 8-byte groups of 8 e4m3 values (fp8 MFMA) -----------
 template <typename T, bool Q8> struct Op {
@@ -106,6 +128,15 @@ ConvArgs<_Float16> ds_args_f16(const ydbl_dsconv_desc* d);
 int ds_check(const ydbl_dsconv_desc* d);
 bool try_dsc_lean(const ConvArgs<_Float16>& a, const float* dww, const float* dwb, int dw_act, int k, int st, int dil,
                   hipStream_t s);
+// sparse_box.hip: the launches of the sparse box path's class tail, in a translation unit (and device code object) of
+// their own.  Arguments with sk_deferred(), k 3 / stride 1 / 64 outputs (ds_check).
+//   ds_defer_tile   the chunked kernel's tile (th x 8, cseg, dbuf) as launch_ds_tile picks it; false: no such instance
+//   lean_defer_tile the one-round-trip 64 -> 64 tile
+//   ds_zero_counts_masks  the counter-zeroing kernel that also zeroes the tile masks
+bool ds_defer_tile(const ConvArgs<_Float16>& a, const float* dww, const float* dwb, int dw_act, int th, int cseg,
+                   bool dbuf, hipStream_t s);
+void lean_defer_tile(const ConvArgs<_Float16>& a, const float* dww, const float* dwb, int dw_act, hipStream_t s);
+void ds_zero_counts_masks(int* counts, int n, unsigned char* masks, int nbytes, hipStream_t s);
 
 template <typename T>
 __device__ __forceinline__ f32x4 mfma_chunk(const typename Vec<T>::type& a, const typename Vec<T>::type& b, f32x4 c);
@@ -287,7 +318,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs<T>& p, const f32x4 
 // and, with a candidate sink, offers the pixel as an anchor: the four lanes are the decode's quad (lane g = side g
 // and class g), the logits are taken as stored (the decode reads the fp16 values), and the level's box launch has
 // run before this one, so a quad that holds a candidate reads its 64 box logits from the level buffer.
-template <typename T, bool SINK>
+// SINK_DEFER: the level's box launch runs after this one; the quad flags its tile instead of decoding (decode_math.hpp).
+template <typename T, int SINK>
 __device__ __forceinline__ void tail_store(const ConvArgs<T>& p, const float (&part)[4], int64_t pix, bool ok, int g) {
   T lv[4];
 #pragma unroll
@@ -304,8 +336,14 @@ __device__ __forceinline__ void tail_store(const ConvArgs<T>& p, const float (&p
       const int b = (int)pix / hw, loc = (int)pix - b * hw;
       const int gy = loc / p.Wo, gx = loc - gy * p.Wo;
       auto logit = [&](int j) { return float(j == 0 ? lv[0] : j == 1 ? lv[1] : j == 2 ? lv[2] : lv[3]); };
-      quad_candidates<T, 16>(p.sk, b, g, ok, p.nt3, logit, p.skbox + pix * p.skboxcs, gx, gy, p.skstride,
-                             p.ska0 + loc);
+      if constexpr (SINK == SINK_DEFER) {
+        unsigned char* tile = p.sk_mask(b, gy, gx);  // written only where ok
+        quad_candidates<T, 16, true>(p.sk, b, g, ok, p.nt3, logit, static_cast<const T*>(nullptr), gx, gy,
+                                     p.skstride, p.ska0 + loc, tile);
+      } else {
+        quad_candidates<T, 16>(p.sk, b, g, ok, p.nt3, logit, p.skbox + pix * p.skboxcs, gx, gy, p.skstride,
+                               p.ska0 + loc);
+      }
     }
   }
 }
@@ -317,7 +355,7 @@ __device__ __forceinline__ void tail_store(const ConvArgs<T>& p, const float (&p
 // four lane groups are summed by xor-shuffles (fixed order); lane group 0 stores.
 // SINK: the instance also serves a candidate sink (tail_store); the others are the plain tail, instruction for
 // instruction.
-template <typename T, int TN, int TM, bool SINK = false>
+template <typename T, int TN, int TM, int SINK = SINK_NONE>
 __device__ __forceinline__ void conv_tail_1x1(const ConvArgs<T>& p, const f32x4 (&acc)[TN][TM], const int64_t (&pp)[TM],
                                               const bool (&pv)[TM], const int (&co)[TN], int g) {
   float bv[TN][4], wv[TN][4][4];
@@ -353,7 +391,7 @@ __device__ __forceinline__ void conv_tail_1x1(const ConvArgs<T>& p, const f32x4 
 // recomputed.  Lanes of one pixel share pv, so the xor-shuffles only mix lanes of the same pixel.
 // s_t: the weights [4][Cout] staged in LDS (rows past nt3 zero), or nullptr to read them from global memory (a
 // late round trip of 16 x nt3 scalar loads per lane at the very end of the launch: kbench pair 64+tail @80^2 bs16 24.8 vs 20.5 us, profiles/r05/r05_bias_lds_ab.txt).
-template <typename T, int TN, int TM, bool SINK = false>
+template <typename T, int TN, int TM, int SINK = SINK_NONE>
 __device__ __forceinline__ void conv_tail_1x1_vals(const ConvArgs<T>& p, const float (&ys)[TN][TM][4],
                                                    const int64_t (&pp)[TM], const bool (&pv)[TM], const int (&co)[TN],
                                                    int g, const float* s_t = nullptr) {

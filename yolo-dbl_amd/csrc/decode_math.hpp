@@ -117,6 +117,14 @@ __device__ __forceinline__ void cand_write(const CandSink& k, int b, int slot, c
   }
 }
 
+// cand_write without the box: the deferred sink (the level's box launch fills cand_box afterwards, bneck.hip)
+__device__ __forceinline__ void cand_write_nobox(const CandSink& k, int b, int slot, float sc, int cls, int idx) {
+  if (slot >= 0 && slot < k.cap) {
+    const int64_t o = (int64_t)b * k.cap + slot;
+    k.cscore[o] = sc; k.ccls[o] = cls; k.cidx[o] = idx;
+  }
+}
+
 // One anchor's candidates, classes first: the four lanes of a quad call it together (lane s = side s and the
 // classes s, s + 4, ...; the quad's lanes are QS apart in the wave).  The box -- 64 logits read, 64 exponentials --
 // is decoded only in quads that hold a candidate (a percent or two of the anchors at predict thresholds); the
@@ -125,9 +133,12 @@ __device__ __forceinline__ void cand_write(const CandSink& k, int b, int slot, c
 //   logit   j -> class j's logit as stored (the activation dtype's value)
 //   bp      the anchor's 64 box logits (16-byte aligned); read only where the quad holds a candidate
 //   pos     the anchor's candidate index (pos * nc + class when multi-label)
-template <typename T, int QS, typename F>
+// DEFER (the sparse box path): same filter, same scores, same slots, but no box is read or written; a quad that holds
+// a candidate stores 1 into *tile, the mask byte of the anchor's 8 x 16 tile (racing quads store the same value).
+template <typename T, int QS, bool DEFER = false, typename F>
 __device__ __forceinline__ void quad_candidates(const CandSink& k, int b, int s, bool ok, int nc, F&& logit,
-                                                const T* bp, int gx, int gy, float st, int pos) {
+                                                const T* bp, int gx, int gy, float st, int pos,
+                                                unsigned char* tile = nullptr) {
   float best = -1.f;
   int bj = 0;
   int any = 0;
@@ -148,6 +159,22 @@ __device__ __forceinline__ void quad_candidates(const CandSink& k, int b, int s,
   } else {
     quad_first_max<QS>(best, bj);
     want = ok && best > k.conf && class_ok(bj, k.classes, k.ncls);
+  }
+  if constexpr (DEFER) {
+    if (want) {  // whole quads
+      if (s == 0) *tile = 1;
+      if (k.multi) {
+        for (int j = s; j < nc; j += 4) {
+          const float sc = cls_score(logit(j));
+          const int slot = wave_slot(k.ccount + b, sc > k.conf && class_ok(j, k.classes, k.ncls));
+          cand_write_nobox(k, b, slot, sc, j, pos * nc + j);
+        }
+      }
+    }
+    if (k.multi) return;
+    const int slot = wave_slot(k.ccount + b, s == 0 && want);
+    cand_write_nobox(k, b, slot, best, bj, pos);
+    return;
   }
   f32x4 box = f32x4{0.f, 0.f, 0.f, 0.f};
   if (want) {  // whole quads

@@ -78,6 +78,12 @@ bool try_dsc_lean(const ConvArgs<_Float16>& a, const float* dww, const float* dw
   // (400 tiles at 80^2) the lean kernel's 512-thread one-round-trip tiles lost to the chunked kernel:
   // +43 / +35 ms over the bench's profile run (profiles/r03/r03rec_c{3,4}_*).
   if (c >= 128 && lean_tiles8(a) > LEAN_MAX_TILES_WIDE) return false;
+  // the deferred sink (sparse box path): its one lean instance, 64 -> 64 k3 (sparse_box.hip); every other shape goes
+  // to the chunked kernel's deferred instances, never to a tile compiled for the box-reading sink
+  if (a.sk_deferred()) {
+    if (!(st == 1 && k == 3 && c == 64 && co == 64 && a.t3w)) return false;
+    return lean_defer_tile(a, dww, dwb, dw_act, s), true;
+  }
   if (st == 1 && k == 3) {
     if (c == 64 && co == 64) return lean_go<64, 64, 3, 1, 8, 8, 256>(a, dww, dwb, dw_act, s), true;
     if (c == 128 && co == 128) return lean_go<128, 128, 3, 1, 8, 8, 512>(a, dww, dwb, dw_act, s), true;

@@ -21,7 +21,9 @@ struct LeanLds {
 
 // One TH x TW output tile (linear tile index `tile`: image-major, then tile row, tile column).
 // smem: LeanLds::BYTES of LDS, 16-byte aligned.
-template <int C, int CO, int K, int S, int TH, int TW, int NT, bool TAIL>
+// DEFER (TAIL only): the tail's candidate sink in its deferred mode (conv_common.hpp, SINK_DEFER), for the kernel
+// instance of the sparse box path.
+template <int C, int CO, int K, int S, int TH, int TW, int NT, bool TAIL, bool DEFER = false>
 __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const float* __restrict__ dww,
                                           const float* __restrict__ dwb, int dw_act, int tile, int tiles_x,
                                           int tiles_y, unsigned char* smem) {
@@ -326,7 +328,8 @@ __device__ __forceinline__ void lean_tile(const ConvArgs<_Float16>& p, const flo
       epilogue(ActC<ACT_RT>{}, ActC<-1>{});
     }
     if constexpr (TAIL && NCG == 1 && TN == 4) {  // Detect class conv over the 64 output channels (CO == 64)
-      conv_tail_1x1_vals<T, TN, TM, true>(p, ys, pp, pv, co, g, reinterpret_cast<const float*>(smem + L::T));
+      conv_tail_1x1_vals<T, TN, TM, DEFER ? SINK_DEFER : SINK_BOX>(p, ys, pp, pv, co, g,
+                                                                   reinterpret_cast<const float*>(smem + L::T));
     }
   }
 }

@@ -51,7 +51,10 @@ class DsConvDesc(C.Structure):
                 ("cand_idx", C.c_void_p), ("cand_count", C.c_void_p), ("cand_cap", C.c_int32),
                 ("conf_thres", C.c_float), ("multi_label", C.c_int32), ("nclasses", C.c_int32),
                 ("classes", C.c_void_p), ("level_stride", C.c_float), ("anchor0", C.c_int32), ("box", View),
-                ("zero_counts", C.c_int32), ("y_unused", C.c_int32)]
+                ("zero_counts", C.c_int32), ("y_unused", C.c_int32),
+                # the sink's deferred mode (sparse box path): the candidates' 8 x 16 tiles flagged, no box read
+                ("tile_mask", C.c_void_p), ("mask_tiles_x", C.c_int32), ("mask_tiles_img", C.c_int32),
+                ("mask_zero", C.c_void_p), ("mask_zero_bytes", C.c_int32)]
     g2_w = g0_w = None  # not in the ABI: bench.py's roofline still asks every DSConv descriptor for these two
 
 
@@ -126,7 +129,11 @@ class LskDesc(C.Structure):
 
 class BottleneckDesc(C.Structure):
     _fields_ = [("x", View), ("y", View), ("c", C.c_int32), ("add", C.c_int32), ("tile_h", C.c_int32),
-                ("params", C.c_void_p), ("c_mid", C.c_int32), ("pw", C.c_int32)]
+                ("params", C.c_void_p), ("c_mid", C.c_int32), ("pw", C.c_int32),
+                # sparse box launch (pw only): the tile mask and the candidate sink that decodes the boxes
+                ("tile_mask", C.c_void_p), ("cand_box", C.c_void_p), ("cand_idx", C.c_void_p),
+                ("cand_count", C.c_void_p), ("cand_cap", C.c_int32), ("level_stride", C.c_float),
+                ("anchor0", C.c_int32), ("nc", C.c_int32), ("multi_label", C.c_int32)]
 
 
 class LetterboxDesc(C.Structure):

@@ -10,6 +10,8 @@ layout used by the multi-GPU path.
 from __future__ import annotations
 
 import ctypes as C
+import os
+import warnings
 import weakref
 
 import torch
@@ -84,7 +86,12 @@ class DetectSession:
     as k independent branches of ONE hipGraph (runtime.BranchGraphRunner; eager mode: one HIP stream per plan).
     At DBL-n/s sizes every launch is short and ramp/tail-bound, so two concurrent half-batch branches fill each
     other's gaps (scripts/stream_probe.py: DBL-n bs32 +10 %, DBL-s bs64 +14 %; one two-branch graph instead of
-    two graphs on two streams a further +2.5 %, scripts/graph_branch_probe.py)."""
+    two graphs on two streams a further +2.5 %, scripts/graph_branch_probe.py).
+
+    sparse_box: the session runs the sparse box path (_sparse_box) -- its P3 / P4 box logits exist only
+    in the 8 x 16 tiles that hold an NMS candidate of the last batch (see feats())."""
+
+    sparse_box = False
 
     def __init__(self, model, batch: int, h: int, w: int, dtype=torch.float16, conf=0.25, iou=0.7, max_det=300,
                  multi_label=False, agnostic=False, classes=None, max_nms=30000, max_wh=7680, clip=True,
@@ -172,6 +179,10 @@ class DetectSession:
         # No decode pass when every level's class conv is the tail of a DWConv -> Conv1x1 launch (DBL-n, nc <= 4,
         # fp16) and no prediction tensor is wanted: those launches emit the candidates themselves (_fuse_candidates)
         self.fused_candidates = self.pred is None and self._fuse_candidates(plan, cm.levels, dd)
+        # The sparse box path on top of that (predict thresholds, fp16 operands only: the fp8 calibration reads
+        # feats(), and below PER_IMAGE_NMS_CONF most tiles hold a candidate): _sparse_box
+        self.sparse_box = bool(self.fused_candidates and nms and not self.fp8 and self.conf >= PER_IMAGE_NMS_CONF
+                               and not os.environ.get("YDBL_NO_SPARSE_BOX") and self._sparse_box(plan, cm.levels, dd))
         if not self.fused_candidates:
             plan.launch("ydbl_detect_decode", dd, what="Detect.decode", keep=[dd])
         nd = NmsDesc(self.cand_box.data_ptr(), self.cand_score.data_ptr(), self.cand_cls.data_ptr(),
@@ -214,6 +225,55 @@ class DetectSession:
             a0 += lv.h * lv.w
         return True
 
+    def _sparse_box(self, plan: Plan, levels, dd: DecodeDesc) -> bool:
+        """The sparse box path (include/ydbl.h: the deferred sink of ydbl_dsconv_desc, the tile mask and candidate
+        sink of ydbl_bottleneck_desc), on the levels whose box branch is ONE ydbl_bottleneck_nhwc launch with pw = 1
+        (emit_detect_box: DBL-n P3 / P4): the level's box launch moves behind its class tail, the tail flags the
+        8 x 16 tiles that hold a candidate instead of decoding, and the box launch computes only those tiles and
+        decodes the candidates' boxes.  One mask buffer for all such levels, zeroed by the launch that zeroes the
+        counters.  The other levels (20^2: three generic convs) keep their order and today's sink.  False, with
+        nothing touched, when no level qualifies."""
+        tails, boxes = {}, {}
+        for k, st in enumerate(plan.steps):
+            name = st.fn.__name__
+            if name == "ydbl_dsconv_nhwc" and st.args[0].tail_w and st.args[0].cand_count:
+                tails[st.args[0].tail_y.ptr] = k
+            elif name == "ydbl_bottleneck_nhwc" and st.args[0].pw:
+                boxes[st.args[0].y.ptr] = k
+        picks = []
+        for i, lv in enumerate(levels):
+            kb, kt = boxes.get(dd.box[i].ptr), tails.get(dd.cls[i].ptr)
+            if kb is not None and kt is not None and kb < kt:
+                picks.append((i, kb, kt, -(-lv.w // 16), -(-lv.h // 8)))
+        if not picks:
+            return False
+        sizes = [levels[i].n * tx * ty for i, _, _, tx, ty in picks]
+        mask = torch.zeros(sum(sizes), dtype=torch.uint8, device=plan.device)
+        plan.buffers.append(mask)
+        self.tile_masks, off, after = {}, 0, {}
+        for (i, kb, kt, tx, ty), size in zip(picks, sizes):
+            self.tile_masks[i] = mask[off:off + size].view(levels[i].n, ty, tx)
+            td, bd = plan.steps[kt].args[0], plan.steps[kb].args[0]
+            td.tile_mask, td.mask_tiles_x, td.mask_tiles_img = mask.data_ptr() + off, tx, tx * ty
+            bd.tile_mask = mask.data_ptr() + off
+            bd.cand_box, bd.cand_idx, bd.cand_count, bd.cand_cap = dd.cand_box, dd.cand_idx, dd.cand_count, dd.cap
+            bd.level_stride, bd.anchor0, bd.nc, bd.multi_label = td.level_stride, td.anchor0, dd.nc, dd.multi_label
+            after[kt] = plan.steps[kb]
+            off += size
+        for st in plan.steps:  # the call that zeroes the counters zeroes the masks too
+            if st.fn.__name__ == "ydbl_dsconv_nhwc" and st.args[0].cand_count and st.args[0].zero_counts:
+                st.args[0].mask_zero, st.args[0].mask_zero_bytes = mask.data_ptr(), mask.numel()
+        moved = {id(s) for s in after.values()}
+        steps = []
+        for k, st in enumerate(plan.steps):  # class branch first, the level's box launch right behind its tail
+            if id(st) in moved:
+                continue
+            steps.append(st)
+            if k in after:
+                steps.append(after[k])
+        plan.steps = steps
+        return True
+
     def _init_split(self, model, batch, h, w, dtype, conf, iou, max_det, multi_label, agnostic, classes, max_nms,
                     max_wh, clip, keep_pred, use_graph, device, fp8, streams, nms, outputs):
         from ..parallel import shard_bounds
@@ -244,6 +304,7 @@ class DetectSession:
         self.use_graph = use_graph
         self._graph = None  # all sub-batch plans as branches of one hipGraph (runtime.BranchGraphRunner)
         self.nc, self.A = self.children[0].nc, self.children[0].A
+        self.sparse_box = all(c.sparse_box for c in self.children)
         self._init_slots()
 
     @property
@@ -374,6 +435,9 @@ class DetectSession:
         session's fp8_fraction).  Returns the number of convs switched."""
         from ..quant import Fp8Calibration, enable_fp8
 
+        if self.sparse_box:
+            raise RuntimeError("calibrate_fp8() on a sparse_box session: the calibration reads feats(), whose box logits "
+                               "outside candidate tiles are not computed; build the session with fp8=...")
         if isinstance(calibration, (str, bytes)) or hasattr(calibration, "__fspath__"):
             calibration = Fp8Calibration.load(calibration)
         if x is not None and calibration is None:
@@ -444,7 +508,15 @@ class DetectSession:
 
     def feats(self):
         """Per-level head maps [B, 64+nc, H_i, W_i]: NCHW views of the plan's level buffers (no copy); a split
-        session concatenates its sub-batch plans' maps (a copy)."""
+        session concatenates its sub-batch plans' maps (a copy).
+
+        A sparse_box session does NOT compute the box logits (channels 0..63) of its P3 / P4 maps outside the 8 x 16
+        tiles that hold an NMS candidate: there the buffers keep whatever an earlier batch left.  The class logits and
+        the 20^2 level are complete.  The call warns about it; for full maps build the session with keep_pred=True
+        or under YDBL_NO_SPARSE_BOX=1."""
+        if self.sparse_box:
+            warnings.warn("feats() of a sparse_box session: box logits outside the tiles that hold an NMS candidate "
+                          "are not computed (keep_pred=True or YDBL_NO_SPARSE_BOX=1 give full maps)", stacklevel=2)
         if self.children:
             per = [c.compiled.feats() for c in self.children]
             return [torch.cat([f[i] for f in per]) for i in range(len(per[0]))]

@@ -1297,7 +1297,9 @@ class Detect(PlanModule):
         return lambda: (pred.to(dt, copy=True), [lv.nchw().contiguous() for lv in levels])
 
     def emit(self, plan, xs, out=None):
-        """Per level: one NHWC buffer [B,h,w,64+nc] (box logits | class logits) = the reference's x[i]."""
+        """Per level: one NHWC buffer [B,h,w,64+nc] (box logits | class logits) = the reference's x[i].  Box branch
+        first; a DetectSession on the sparse box path moves the one-launch box branch of a level behind the level's
+        class tail once it knows its thresholds (engine.session.DetectSession._sparse_box)."""
         levels = []
         for i, x in enumerate(xs):
             lv = plan.alloc(x.n, x.h, x.w, self.no)
