@@ -61,6 +61,8 @@
  *                             engine/validator.py:222-262, non-scipy branch)
  *   ydbl_confusion_matrix  <- ConfusionMatrix.process_batch utils/metrics.py:326-382 and its call sites in
  *                             DetectionValidator.update_metrics models/yolo/detect/val.py:140-159
+ *   ydbl_global_avgpool    <- BaseModel._predict_once with embed set, nn/tasks.py:168-169
+ *                             (adaptive_avg_pool2d(x, (1, 1)).squeeze(-1).squeeze(-1) of a layer's output)
  */
 #ifndef YDBL_H
 #define YDBL_H
@@ -588,6 +590,27 @@ typedef struct {
 } ydbl_confusion_desc;
 int64_t ydbl_confusion_workspace(int32_t n, int32_t max_det, int32_t n_gt);
 int ydbl_confusion_matrix(const ydbl_confusion_desc* d, void* stream);
+
+/* Global average pool of an NHWC view: y[n][c] = mean over (h, w) of x[n][.][.][c], the pooled layer feature of
+ * BaseModel._predict_once with embed set (nn/tasks.py:168-169: adaptive_avg_pool2d(x, (1, 1)).squeeze(-1).squeeze(-1)).
+ * fp32 accumulation, mean = sum / float(h*w) in fp32, one round-to-nearest-even to x's dtype.  Deterministic: no
+ * floating-point atomics; the pixels of an image are cut into chunks by (h*w, c, dtype) alone -- never by n -- and
+ * added in a fixed order, so image i's row has the same bits pooled alone, inside any batch and on every run.
+ * More than one chunk per image: the chunks' fp32 partial rows go through `workspace` and a second launch on the same
+ * stream adds them (ydbl_global_avgpool_workspace(d) bytes, 0 for a map of one chunk; 4-byte aligned; -1 for a
+ * descriptor ydbl_global_avgpool would reject for its view).  x may be a channel slice (cs >= c, any element offset):
+ * 16-byte loads when c, cs and the pointer allow them (multiples of 8 halves / 4 floats), else a scalar path --
+ * never YDBL_EINVAL for alignment.  n <= 65535.  YDBL_EINVAL: null descriptor / x.ptr / y, empty view, bad dtype,
+ * y_stride < c, workspace NULL or too small when one is needed.  No allocation, graph-capturable, reentrant. */
+typedef struct {
+  ydbl_view x;            /* NHWC view (channel slice allowed: cs >= c, any offset), YDBL_F16 or YDBL_F32 */
+  void* y;                /* row n at y + n * y_stride elements, c elements, in x's dtype */
+  int64_t y_stride;       /* elements; >= x.c (so several layers share one [B, D] row) */
+  void* workspace;        /* fp32 partial sums, >= ydbl_global_avgpool_workspace(d) bytes; may be NULL when that is 0 */
+  int64_t workspace_bytes;
+} ydbl_avgpool_desc;
+int64_t ydbl_global_avgpool_workspace(const ydbl_avgpool_desc* d);
+int ydbl_global_avgpool(const ydbl_avgpool_desc* d, void* stream);
 
 const char* ydbl_last_error(void);
 const char* ydbl_version(void);

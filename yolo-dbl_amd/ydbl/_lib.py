@@ -160,6 +160,12 @@ class AreaAttnDesc(C.Structure):
                 ("scale", C.c_float)]
 
 
+class AvgPoolDesc(C.Structure):
+    """ydbl_avgpool_desc: global average pool of an NHWC view into rows of a [B, D] buffer (Model.embed)."""
+    _fields_ = [("x", View), ("y", C.c_void_p), ("y_stride", C.c_int64), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64)]
+
+
 # name -> (argtypes, restype); every entry must exist in include/ydbl.h
 _P = C.c_void_p
 _VP = C.POINTER(View)
@@ -214,6 +220,8 @@ SIGNATURES = {
     "ydbl_match_predictions": ([C.POINTER(MatchDesc), _P], C.c_int),
     "ydbl_confusion_workspace": ([C.c_int32, C.c_int32, C.c_int32], C.c_int64),
     "ydbl_confusion_matrix": ([C.POINTER(ConfusionDesc), _P], C.c_int),
+    "ydbl_global_avgpool_workspace": ([C.POINTER(AvgPoolDesc)], C.c_int64),
+    "ydbl_global_avgpool": ([C.POINTER(AvgPoolDesc), _P], C.c_int),
     "ydbl_last_error": ([], C.c_char_p),
     "ydbl_version": ([], C.c_char_p),
 }

@@ -19,9 +19,9 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from ..nn.tasks import DetectionModel, weights_signature, ydbl_env
+from ..nn.tasks import DetectionModel, normalize_embed, weights_signature, ydbl_env
 from .results import Results
-from .session import AugmentSession, DetectSession, default_streams
+from .session import AugmentSession, DetectSession, EmbedSession, default_streams
 
 DEFAULTS = {"conf": 0.25, "iou": 0.7, "max_det": 300, "half": False, "fp8": False, "device": None, "agnostic_nms": False,
             "classes": None, "batch": 1, "verbose": False, "imgsz": 640,
@@ -30,7 +30,9 @@ DEFAULTS = {"conf": 0.25, "iou": 0.7, "max_det": 300, "half": False, "fp8": Fals
             # fp8: an ydbl.quant.Fp8Calibration or its JSON file (None: calibrate on the first batch)
             "fp8_calibration": None,
             # test-time augmentation (U/nn/tasks.py:361-398): three passes (1, 0.83 flipped, 0.67), one NMS
-            "augment": False}
+            "augment": False,
+            # layer indices whose pooled outputs predict() returns instead of Results (U/cfg/default.yaml:67)
+            "embed": None}
 
 
 def check_augment(augment, fp8=False, gather_rows=None) -> bool:
@@ -42,6 +44,24 @@ def check_augment(augment, fp8=False, gather_rows=None) -> bool:
     if augment and gather_rows is not None:
         raise NotImplementedError("augment=True is not implemented for the batch-sharded predictor (gather_rows)")
     return bool(augment)
+
+
+def check_embed(embed, n_layers: int, augment=False, fp8=False, gather_rows=None):
+    """embed's guards, before any device work: the normalised layer tuple (nn.tasks.normalize_embed; ValueError for
+    an index outside [0, n_layers - 2] or a non-integer), or None when no embedding is asked for.  augment=True has
+    no embedding (the reference silently ignores embed there: ValueError); fp8 and the batch-sharded predictor's
+    record rows are not implemented for it."""
+    if embed is None or (isinstance(embed, (list, tuple)) and not embed):
+        return None
+    embed = normalize_embed(embed, n_layers)
+    if augment:
+        raise ValueError("embed with augment=True: the augmented forward returns no embedding (the reference "
+                         "silently ignores embed there); drop one of the two")
+    if fp8:
+        raise NotImplementedError("embed with fp8 is not implemented; use half=True")
+    if gather_rows is not None:
+        raise NotImplementedError("embed is not implemented for the batch-sharded predictor (gather_rows)")
+    return embed
 
 
 def select_device(device=None) -> torch.device:
@@ -234,16 +254,32 @@ class Model:
 
     def session(self, batch, h, w, half=False, conf=0.25, iou=0.7, max_det=300, agnostic=False, classes=None,
                 multi_label=False, device=None, keep_pred=False, use_graph=True, fp8=False, clip=True,
-                streams=1, gather_rows=None, nms=True, fp8_calibration=None, augment=False) -> DetectSession:
+                streams=1, gather_rows=None, nms=True, fp8_calibration=None, augment=False, embed=None):
         """A compiled (batch, h, w, dtype, NMS settings) inference session; streams > 1 splits the batch into
         that many concurrently replayed sub-batch graphs (DetectSession); streams=None: default_streams(batch),
         the layout predict() runs and bench.py times.  augment=True: the test-time-augmentation session
-        (AugmentSession: three passes, one NMS over their union; no fp8)."""
+        (AugmentSession: three passes, one NMS over their union; no fp8).  embed=[i, ...]: an EmbedSession -- the
+        plan stops at layer max(embed) and returns the pooled layer features; the detection arguments (conf, iou, NMS
+        settings) mean nothing to it and are not part of its cache key."""
+        embed = check_embed(embed, len(self.model.model), augment, fp8, gather_rows)
         augment = check_augment(augment, fp8, gather_rows)
         if streams is None:
             streams = default_streams(batch)
         dev = select_device(device)
         dtype = torch.float16 if (half or fp8) else torch.float32
+        if embed is not None:
+            key = ("embed", embed, batch, h, w, dtype, str(dev), use_graph, int(streams), ydbl_env())
+            s = self._sessions.get(key)
+            if s is None:
+                while len(self._sessions) >= self.MAX_SESSIONS:
+                    self._sessions.popitem(last=False)
+                with torch.cuda.device(dev):
+                    s = EmbedSession(self.model, batch, h, w, dtype, embed, dev, int(streams), use_graph=use_graph)
+                s.wsig = weights_signature(self.model)
+                self._sessions[key] = s
+            else:
+                self._sessions.move_to_end(key)
+            return s
         key = (batch, h, w, dtype, float(conf), float(iou), int(max_det), bool(agnostic),
                tuple(classes) if classes is not None else None, bool(multi_label), str(dev), keep_pred, use_graph,
                float(fp8), bool(clip), int(streams), gather_rows, bool(nms),
@@ -304,10 +340,14 @@ class Model:
 
         args = {**DEFAULTS, **self.overrides, **kwargs}
         check_augment(args["augment"], args["fp8"])
+        args["embed"] = check_embed(args["embed"], len(self.model.model), args["augment"], args["fp8"])
         dev = select_device(args["device"])
         t0 = time.perf_counter()
         if source is None:
             raise ValueError("predict() needs a source (no default asset is bundled)")
+        if args["embed"] is not None:
+            gen = self._embed_source(source, args, dev)
+            return gen if stream else list(gen)
         if not isinstance(source, torch.Tensor) and not (isinstance(source, (list, tuple)) and source
                                                          and isinstance(source[0], torch.Tensor)):
             if check_path_source(source):
@@ -366,6 +406,56 @@ class Model:
         results = [Results(lambda i=i: hwc[i], path=f"image{i}.jpg", names=names, speed=speed, orig_shape=shape,
                            boxes=lambda i=i: box(i)) for i in range(b)]
         return iter(results) if stream else results
+
+    def _embed_source(self, source, args, dev):
+        """predict(embed=[...]): a generator of one 1-D tensor [D] per image in source order (the predictor yields
+        the embedding tensors instead of Results, U/engine/predictor.py:260-261), for every source kind predict()
+        takes; on the model's device, fp16 under half=True and fp32 otherwise.  Each batch's [B, D] output is copied
+        out of the session once and its rows handed over (the session's buffer is reused by the next call)."""
+        from .preprocess import letterbox_batch
+        from .sources import check_path_source, file_batches, frames_from_images, is_frame_source
+
+        if not isinstance(source, torch.Tensor) and not (isinstance(source, (list, tuple)) and source
+                                                         and isinstance(source[0], torch.Tensor)):
+            if check_path_source(source):
+                batches = (frames for _, frames in file_batches(source, args["batch"]))
+            elif is_frame_source(source):
+                batches = iter([frames_from_images(source)[1]])
+            else:
+                raise TypeError(f"unsupported source type {type(source).__name__}")
+            imgsz = args["imgsz"]
+            imgsz = (imgsz, imgsz) if isinstance(imgsz, int) else tuple(imgsz)
+            stride = int(self.model.stride.max())
+            for frames in batches:
+                frames = [frames] if isinstance(frames, np.ndarray) and frames.ndim == 3 else list(frames)
+                yield from self._embed_batch(letterbox_batch(frames, imgsz, stride=stride, device=dev), args, dev)
+            return
+        im = check_tensor_source(source, int(self.model.stride.max()))
+        if im.device != dev:  # host tensors are scaled on the host, as in predict()
+            im = load_tensor_source(im).to(dev, non_blocking=True).float()
+        yield from self._embed_batch(im, args, dev, load_tensor=True)
+
+    def _embed_batch(self, im, args, dev, load_tensor=False):
+        b, _, h, w = im.shape
+        kw = dict(half=args["half"], device=dev, streams=args["streams"], embed=args["embed"])
+        scale = None
+        if load_tensor:  # LoadTensor's /255 rule on the device, without a host sync (as predict()'s copy path)
+            one, inv = _scale_consts(dev)
+            thr = 1.0 + (torch.finfo(im.dtype).eps if im.is_floating_point() else 0.0)
+            scale = torch.where(im.amax() > thr, inv, one)
+        s = self.session(b, h, w, **kw)
+        out = s(im, scale)
+        if self._stale(s):  # weights edited since the session was compiled: rebuild and run again
+            out = self.session(b, h, w, **kw)(im, scale)
+        return out.clone().unbind(0)
+
+    def embed(self, source=None, stream=False, **kwargs):
+        """U/engine/model.py:467-499: image embeddings -- predict() with embed defaulting to the second-to-last
+        layer (the DBL configs' last P5 FullPAD_Tunnel: 256 channels at scale n).  A list of 1-D tensors, one per
+        image (a generator with stream=True)."""
+        if not kwargs.get("embed"):
+            kwargs["embed"] = [len(self.model.model) - 2]
+        return self.predict(source, stream, **kwargs)
 
     def _predict_frames(self, frames, args, dev, t0, stream, paths=None):
         from .preprocess import letterbox_batch, scale_boxes

@@ -662,3 +662,78 @@ class AugmentSession(DetectSession):
     def feats(self):
         """None: the reference's augmented forward returns (y, None) (U/nn/tasks.py:376)."""
         return None
+
+
+class EmbedSession:
+    """``embed=[i, ...]``: pooled layer features instead of detections (Model.embed, U/engine/model.py:467-499;
+    _predict_once's early return, U/nn/tasks.py:158-171).  The compiled plan stops at layer max(embed) -- no Detect
+    branches, no decode, no NMS -- with one ydbl_global_avgpool behind each named layer; ``out [B, D]`` (D = the
+    layers' channel counts summed, ascending layer order, plan dtype) is owned by the session and rewritten by the
+    next call.
+
+    streams = k > 1 splits the batch into k contiguous sub-batches (parallel.shard_bounds, as DetectSession): one
+    plan per sub-batch, each writing its rows of the one shared ``out``, captured as the branches of ONE hipGraph
+    (runtime.BranchGraphRunner); streams == 1 replays one GraphRunner.  Every plan passes Plan.check_single_stream.
+    The batch goes through the staging copy (load(), with LoadTensor's /255 rule as its scale argument); there is no
+    in-place input binding (launch_bound) for these sessions."""
+
+    def __init__(self, model, batch: int, h: int, w: int, dtype=torch.float16, embed=None, device="cuda", streams=1,
+                 use_graph=True, _out=None):
+        from ..nn.tasks import _propagate_shapes, normalize_embed
+
+        self.embed = normalize_embed(embed, len(model.model))
+        self.model, self.batch, self.h, self.w, self.dtype = model, batch, h, w, dtype
+        self.use_graph, self._graph, self.children, self.bounds = use_graph, None, [], None
+        dev = torch.device(device)
+        if streams > 1 and batch >= streams:
+            from ..parallel import shard_bounds
+
+            self.bounds = [shard_bounds(batch, streams, r) for r in range(streams)]
+            # one [B, D] output, each sub-batch plan compiled onto its row slice
+            shapes = _propagate_shapes(list(model.model)[: self.embed[-1] + 1], 1, h, w, model.yaml["ch"])
+            self.dim = sum(shapes[i][3] for i in self.embed)
+            self.out = torch.empty((batch, self.dim), dtype=dtype, device=dev) if _out is None else _out
+            self.children = [EmbedSession(model, b - a, h, w, dtype, self.embed, dev, use_graph=use_graph,
+                                          _out=self.out[a:b]) for a, b in self.bounds]
+            self.streams = [torch.cuda.Stream(dev) for _ in self.children]
+            self.plans = [c.plan for c in self.children]
+            self.plan = self.plans[0]
+            return
+        cm = model.compile(batch, h, w, dtype, device=dev, embed=self.embed, embed_out=_out)
+        self.compiled, self.plan, self.plans = cm, cm.plan, [cm.plan]
+        self.out, self.dim = cm.embed_out, cm.embed_out.shape[1]
+        self.plan.check_single_stream()
+
+    def load(self, x: torch.Tensor, scale: torch.Tensor | None = None):
+        """Copy a BCHW batch into the staging buffer(s), multiplied by `scale` on the way (DetectSession.load)."""
+        if tuple(x.shape) != (self.batch, 3, self.h, self.w):
+            raise ValueError(f"input shape {tuple(x.shape)} != session shape {(self.batch, 3, self.h, self.w)}")
+        if self.children:
+            for c, (a, b) in zip(self.children, self.bounds):
+                c.load(x[a:b], scale)
+        elif scale is None:
+            self.compiled.input.copy_(x, non_blocking=True)
+        else:
+            torch.mul(x if x.dtype == torch.float32 else x.float(), scale, out=self.compiled.input)
+
+    def launch(self):
+        if self.use_graph:
+            if self._graph is None:
+                self._graph = BranchGraphRunner(self.plans) if self.children else GraphRunner(self.plan)
+            self._graph.replay()
+        elif self.children:  # eager: each sub-batch plan on its own stream, then join
+            cur = torch.cuda.current_stream(self.out.device)
+            for c, st in zip(self.children, self.streams):
+                st.wait_stream(cur)
+                with torch.cuda.stream(st):
+                    c.plan.run()
+            for st in self.streams:
+                cur.wait_stream(st)
+        else:
+            self.plan.run()
+
+    def __call__(self, x: torch.Tensor | None = None, scale: torch.Tensor | None = None) -> torch.Tensor:
+        if x is not None:
+            self.load(x, scale)
+        self.launch()
+        return self.out

@@ -17,6 +17,7 @@ import ast
 import contextlib
 import json
 import math
+import operator
 import os
 import re
 from copy import deepcopy
@@ -53,6 +54,35 @@ def register_module(cls, name: str | None = None):
     bookkeeping for a plugin name follows the reference's rule for names it does not know (c2 = ch[f])."""
     REGISTRY[name or cls.__name__] = cls
     return cls
+
+
+def normalize_embed(embed, n_layers: int) -> tuple:
+    """The layer indices of ``embed=`` as _predict_once uses them (U/nn/tasks.py:158-171): ascending and each once,
+    whatever the order of the list (the segments are appended in layer order and the forward returns at max(embed)).
+    Valid: integers in [0, n_layers - 2] -- every layer but the head, whose output is no feature map; the reference
+    never returns (index past the model) or fails inside the pool (the head) for the others.  Pure host arithmetic:
+    callers run it before anything is compiled or a device is touched."""
+    if isinstance(embed, (int, float)) and not isinstance(embed, bool):
+        embed = [embed]
+    try:
+        items = list(embed)
+    except TypeError:
+        raise ValueError(f"embed={embed!r}: a list of layer indices expected") from None
+    if not items:
+        raise ValueError("embed: an empty list names no layer")
+    out = set()
+    for i in items:
+        try:
+            if isinstance(i, bool):
+                raise TypeError
+            i = operator.index(i)
+        except TypeError:
+            raise ValueError(f"embed index {i!r} is not an integer (valid layers: 0..{n_layers - 2})") from None
+        if not 0 <= i <= n_layers - 2:
+            raise ValueError(f"embed index {i} is outside the valid layer range 0..{n_layers - 2} "
+                             f"(layer {n_layers - 1} is the detection head)")
+        out.add(i)
+    return tuple(sorted(out))
 
 
 def make_divisible(x, divisor):
@@ -221,15 +251,23 @@ class DetectionModel(nn.Module):
         Runs the compiled HIP plan of x's (batch, h, w, dtype) on x's device -- forward + decode, no NMS --
         replayed as a hipGraph; fp16 input takes the half path (AutoBackend fp16, autobackend.py:145-155).
         BN is folded and the semantics are always inference (eval) ones; training / loss (dict input) and
-        profile / visualize / embed are not on this path.  augment=True: _predict_augment (U/nn/tasks.py:361-398) --
+        profile / visualize are not on this path.  embed=[i, ...]: _predict_once's early return (U/nn/tasks.py:158-171)
+        -- the tuple of B row tensors [sum C_i] in x's dtype, the named layers' pooled outputs in ascending layer
+        order, from a plan that stops at max(embed) (engine.session.EmbedSession).  augment=True: _predict_augment (U/nn/tasks.py:361-398) --
         returns ``(y, None)``, y [B, 4+nc, A_tot] the three passes' de-scaled, de-flipped, tail-clipped predictions
         side by side (engine.session.AugmentSession).  Returns fresh tensors (the plan's buffers are reused by the
         next call).  CPU tensors raise: there is no CPU execution path."""
         if isinstance(x, dict):
             raise NotImplementedError("training loss (dict input) is outside the inference path")
-        if args or any(kwargs.get(k) for k in ("profile", "visualize", "embed")):
-            raise NotImplementedError("profile / visualize / embed are outside the inference path")
+        if args or any(kwargs.get(k) for k in ("profile", "visualize")):
+            raise NotImplementedError("profile / visualize are outside the inference path")
         augment = bool(kwargs.get("augment"))
+        embed = kwargs.get("embed")
+        if embed:  # checked before any device work
+            if augment:
+                raise ValueError("embed with augment=True: the augmented forward has no embedding (the reference "
+                                 "silently ignores embed there)")
+            embed = normalize_embed(embed, len(self.model))
         if not isinstance(x, torch.Tensor) or x.ndim != 4:
             raise TypeError("DetectionModel.forward takes a BCHW tensor")
         if x.device.type != "cuda":
@@ -239,6 +277,14 @@ class DetectionModel(nn.Module):
         if x.shape[1] != self.yaml["ch"]:
             raise ValueError(f"input has {x.shape[1]} channels, the model {self.yaml['ch']}")
         b, _, h, w = x.shape
+        if embed:  # _predict_once's early return (U/nn/tasks.py:168-171): torch.unbind(torch.cat(embeddings, 1), 0)
+            s = self._forward_session(b, h, w, x.dtype == torch.float16, x.device, embed=embed)
+            out = s(x.float())
+            sig = weights_signature(self)
+            if sig != s.wsig:
+                s = self._forward_session(b, h, w, x.dtype == torch.float16, x.device, fresh=sig, embed=embed)
+                out = s(x.float())
+            return out.to(x.dtype, copy=True).unbind(0)
         s = self._forward_session(b, h, w, x.dtype == torch.float16, x.device, augment=augment)
         s(x.float())
         sig = weights_signature(self)  # checked while the graph runs
@@ -251,13 +297,13 @@ class DetectionModel(nn.Module):
         feats = [f.contiguous() for f in s.feats()]
         return y, feats
 
-    def _forward_session(self, b, h, w, half, device, fresh=None, augment=False):
-        from ..engine.session import AugmentSession, DetectSession, default_streams
+    def _forward_session(self, b, h, w, half, device, fresh=None, augment=False, embed=None):
+        from ..engine.session import AugmentSession, DetectSession, EmbedSession, default_streams
 
         cache = self.__dict__.setdefault("_fwd_sessions", {})
         # compiled plans hold the routing of the YDBL_* switches at build time (part of the key) and BN-folded
         # copies of the weights (the session's wsig, checked by forward() after each launch)
-        key = (b, h, w, half, str(device), ydbl_env(), augment)
+        key = (b, h, w, half, str(device), ydbl_env(), augment) + ((embed,) if embed else ())
         s = cache.pop(key, None)
         if s is not None and fresh is not None and s.wsig != fresh:
             s = None  # weights changed since this plan was built
@@ -265,9 +311,13 @@ class DetectionModel(nn.Module):
             while len(cache) >= self.MAX_FORWARD_SESSIONS:
                 cache.pop(next(iter(cache)))
             with torch.cuda.device(device):
-                s = (AugmentSession if augment else DetectSession)(
-                    self, b, h, w, torch.float16 if half else torch.float32, keep_pred=True, nms=False,
-                    device=device, streams=default_streams(b))
+                if embed:
+                    s = EmbedSession(self, b, h, w, torch.float16 if half else torch.float32, embed, device=device,
+                                     streams=default_streams(b))
+                else:
+                    s = (AugmentSession if augment else DetectSession)(
+                        self, b, h, w, torch.float16 if half else torch.float32, keep_pred=True, nms=False,
+                        device=device, streams=default_streams(b))
             s.wsig = weights_signature(self)
         cache[key] = s  # most recently used last
         return s
@@ -290,13 +340,22 @@ class DetectionModel(nn.Module):
     def is_fused(self):
         return self._fused
 
-    def compile(self, batch: int, h: int, w: int, dtype=torch.float16, device="cuda", bind=None) -> "CompiledModel":
+    def compile(self, batch: int, h: int, w: int, dtype=torch.float16, device="cuda", bind=None, embed=None,
+                embed_out=None) -> "CompiledModel":
         """Build the launch plan of one forward: input NCHW fp32 [batch,3,h,w] -> per-level head outputs.
         The plan reads its batch through an input binding (include/ydbl.h ydbl_input_bind): bind_ptr, a device int64
         holding the batch pointer (initially the plan's own staging buffer ``input``), and bind_amax, a device fp32
         batch maximum for LoadTensor's /255 rule (0: scale 1).  bind = (bind_ptr, bind_amax) shares them with a
-        caller (a split session: one word per sub-batch plan, one maximum)."""
+        caller (a split session: one word per sub-batch plan, one maximum).
+
+        embed = layer indices (normalize_embed): the truncated plan of _predict_once's early return
+        (U/nn/tasks.py:158-171).  Layers 0..max(embed) only -- no head, no concat buffer past the cut (a producer whose
+        concat lies past it writes a buffer of its own) -- and right behind the launches of each named layer one
+        ydbl_global_avgpool ("embed.pool") of its output into its columns of ``embed_out`` [batch, sum C_i] (plan
+        dtype; a caller's 2-D view with its own row stride for a split session).  The result has levels = None."""
         plan = Plan(torch.device(device), dtype)
+        if embed is not None:
+            embed = normalize_embed(embed, len(self.model))
         inp = plan.alloc(batch, h, w, 8)  # RGB padded to 8 channels (16-byte vectors)
         x_nchw = torch.empty((batch, self.yaml["ch"], h, w), dtype=torch.float32, device=plan.device)
         plan.buffers.append(x_nchw)
@@ -309,7 +368,37 @@ class DetectionModel(nn.Module):
         ib = _lib.InputBind(bind_ptr.data_ptr(), bind_amax.data_ptr())
         # Concat outputs are allocated up front; their producers write straight into the slices.
         layers = list(self.model)
+        if embed is not None:
+            layers = layers[: embed[-1] + 1]  # nothing past the cut is shaped, allocated or emitted
         shapes = _propagate_shapes(layers, batch, h, w, self.yaml["ch"])
+        pool = None
+        if embed is not None:
+            widths = [shapes[i][3] for i in embed]
+            if embed_out is None:
+                embed_out = torch.empty((batch, sum(widths)), dtype=dtype, device=plan.device)
+            if (tuple(embed_out.shape) != (batch, sum(widths)) or embed_out.dtype != dtype
+                    or embed_out.stride(1) != 1 or embed_out.device.type != plan.device.type):
+                raise ValueError(f"embed_out: a [{batch}, {sum(widths)}] {dtype} view with unit column stride "
+                                 f"on {plan.device} expected")
+            plan.buffers.append(embed_out)
+            col = dict(zip(embed, [sum(widths[:k]) for k in range(len(widths))]))
+            views = {}
+
+            def pool(i, v):
+                """Layer i's output view v -> its columns of embed_out (emitted right behind the layer's launches:
+                no later in-place consumer of v can come between them)."""
+                if i not in col:
+                    return
+                d = _lib.AvgPoolDesc(v.struct(), embed_out.data_ptr() + col[i] * embed_out.element_size(),
+                                     embed_out.stride(0), None, 0)
+                need = int(_lib.lib.ydbl_global_avgpool_workspace(d))
+                if need < 0:
+                    _lib.check(1, "ydbl_global_avgpool_workspace")
+                ws = plan.scratch(need) if need else None
+                if ws is not None:
+                    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+                plan.launch("ydbl_global_avgpool", d, what="embed.pool", keep=[d, v])
+                views[i] = v
         out_hint: dict[int, TV] = {}
         cat_buf: dict[int, TV] = {}
         for m in layers:
@@ -330,6 +419,7 @@ class DetectionModel(nn.Module):
         # layers 0+1 as one kernel when layer 0's map feeds layer 1 only (the full-resolution map never
         # reaches HBM); YDBL_NO_STEM2=1 keeps them separate (A/B switch)
         used_later = any(j == 0 for m in layers[2:] for j in ([m.f] if isinstance(m.f, int) else m.f))
+        used_later = used_later or (embed is not None and 0 in embed)  # layer 0's map is pooled: it must exist
         stem2 = (stem is not None and len(layers) > 1 and not used_later and not os.environ.get("YDBL_NO_STEM2")
                  and M.stem2_ok(layers[0], layers[1], self.yaml["ch"], dtype))
         if stem is None:
@@ -339,22 +429,25 @@ class DetectionModel(nn.Module):
             plan.cur_layer = m.i  # (ydbl.quant names fp8 candidates by the layer that emitted them)
             if stem2 and m is layers[1]:
                 y.append(x)
-                continue
-            if m is stem and stem2:  # preprocess + layers 0 and 1 in one kernel
+            elif m is stem and stem2:  # preprocess + layers 0 and 1 in one kernel
                 x = M.emit_stem2(layers[0], layers[1], plan, x_nchw, batch, self.yaml["ch"], h, w,
                                  cat_buf.get(1, out_hint.get(1)), bind=ib)
                 y.append(None)  # layer 0's map is never materialised
                 continue
-            if m is stem:  # preprocess + first Conv fused, straight from the NCHW batch
+            elif m is stem:  # preprocess + first Conv fused, straight from the NCHW batch
                 x = M.emit_stem(m, plan, x_nchw, batch, self.yaml["ch"], h, w, bind=ib)
                 y.append(x)
-                continue
-            if m.f != -1:
-                x = y[m.f] if isinstance(m.f, int) else [x if j == -1 else y[j] for j in m.f]
-            out = cat_buf.get(m.i, out_hint.get(m.i))
-            x = M.emit_module(m, plan, x, out)
-            y.append(x)
-        cm = CompiledModel(plan, x_nchw, inp, x, self.model[-1])
+            else:
+                if m.f != -1:
+                    x = y[m.f] if isinstance(m.f, int) else [x if j == -1 else y[j] for j in m.f]
+                out = cat_buf.get(m.i, out_hint.get(m.i))
+                x = M.emit_module(m, plan, x, out)
+                y.append(x)
+            if pool is not None:
+                pool(m.i, x)
+        cm = CompiledModel(plan, x_nchw, inp, x if embed is None else None, self.model[-1])
+        if embed is not None:
+            cm.embed, cm.embed_out, cm.embed_views = embed, embed_out, views
         cm.bind_ptr, cm.bind_amax = bind_ptr, bind_amax
         # the InputBind records the launches read (retargeted by CompiledModel.set_bind)
         cm.bind_holders = [st.args[0].bind if st.fn.__name__ == "ydbl_conv_stem2" else st.args[-1]
@@ -366,9 +459,13 @@ class DetectionModel(nn.Module):
 
 class CompiledModel:
     """A compiled forward: ``input`` (NCHW fp32 staging buffer) -> ``levels`` (per-level NHWC head outputs);
-    bind_ptr / bind_amax: its input binding (DetectionModel.compile)."""
+    bind_ptr / bind_amax: its input binding (DetectionModel.compile).  A plan compiled with embed= stops at the last
+    named layer: ``levels`` is None, ``embed`` the normalised indices, ``embed_out`` the [batch, D] pooled features
+    and ``embed_views`` {layer: the output view its pool reads}."""
 
-    def __init__(self, plan: Plan, x_nchw: torch.Tensor, inp: TV, levels: list[TV], detect: M.Detect):
+    embed = embed_out = embed_views = None
+
+    def __init__(self, plan: Plan, x_nchw: torch.Tensor, inp: TV, levels: list[TV] | None, detect: M.Detect):
         self.plan, self.input, self.inp, self.levels, self.detect = plan, x_nchw, inp, levels, detect
 
     def feats(self):
