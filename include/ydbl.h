@@ -45,7 +45,9 @@
  *   ydbl_lsk_gate          <- LSKblock.forward LSKA.py:40-52 (mean/max, 7x7 squeeze, sigmoid gating)
  *   ydbl_lsk_attn/_out     <- LSKblock.forward LSKA.py:43-52 (conv1 | conv2 + stats; gate + conv + x *)
  *   ydbl_hg_*              <- AdaHyperedgeGen/AdaHGConv block.py:1627-1708 (ydbl_hg_fused: the whole
- *                             AdaHGConv incl. pre_head_proj block.py:1645, one call)
+ *                             AdaHGConv incl. pre_head_proj block.py:1645, one call;
+ *                             ydbl_hg_fused_pair: HyperACE's two C3AH branches block.py:1886-1895
+ *                             in one set of launches)
  *   ydbl_detect_decode     <- Detect._inference head.py:143-181 + DFL block.py:79-83 +
  *                             make_anchors/dist2bbox utils/tal.py:333-357 + NMS candidate
  *                             filter utils/ops.py:234-276
@@ -347,6 +349,12 @@ int ydbl_hg_propagate(const ydbl_hg_desc* d, void* stream);
  * ydbl_hg_fused_workspace() bytes, uninitialised memory is fine; -1 = unsupported shape. */
 int64_t ydbl_hg_fused_workspace(int32_t n, int32_t tokens, int32_t dim, int32_t edges, int32_t dtype);
 int ydbl_hg_fused(const ydbl_hg_desc* d, void* stream);
+/* ydbl_hg_fused(d0) followed by ydbl_hg_fused(d1), bit for bit, with both calls' workgroups in each of the five
+ * launches (blockIdx.z picks the descriptor) when the two calls are independent and of one shape: both pass
+ * ydbl_hg_fused's checks, agree in n, h*w, channels, num_edges, num_heads and dtype, neither y shares an element with
+ * the other's x or y (channel slices of one buffer with disjoint ranges are fine), and the workspaces do not
+ * intersect.  Otherwise the two calls run one after the other.  YDBL_EINVAL: a null descriptor. */
+int ydbl_hg_fused_pair(const ydbl_hg_desc* d0, const ydbl_hg_desc* d1, void* stream);
 
 /* Detect decode + NMS candidate extraction.
  * box[l]: fp32 view [n,h_l,w_l,64] (DFL logits), cls[l]: fp32 view [n,h_l,w_l,nc].

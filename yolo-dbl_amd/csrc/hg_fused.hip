@@ -15,6 +15,9 @@
 //   hg3_out   y = GELU(A He3 + bn) + X, A = exp(l - m) / S.
 // (One 1024-thread workgroup per image doing all of it -- the round-2 form -- kept 16 CUs busy for 58 us per
 // call at bs16 while the rest of the chip waited.)  All arithmetic fp32; slices merge in slice order.
+// Every kernel takes the arguments of up to two calls (Hg3Sides) and blockIdx.z picks the side, so two independent
+// calls of one shape (HyperACE's two C3AH branches) share their five launches: ydbl_hg_fused_pair.  A side's
+// workgroups do what the single call's do, on that side's x, y, workspace and weights.
 #include "conv_common.hpp"
 
 namespace ydbl {
@@ -52,15 +55,40 @@ static Hg3Ws hg3_ws(int B, int N, int D, int E) {
   return w;
 }
 
+// one call's arguments: tokens, output, workspace, weights (the Hg3Ws offsets are the same on both sides)
+struct Hg3Side {
+  const void* x;
+  void* y;
+  int xcs, ycs;  // pixel strides of x and y (elements)
+  unsigned char* ws;
+  const float *base, *wc, *bc;  // prototype_base, context_net
+  const void* wp;               // pre_head_proj weight, x's dtype
+  const float *bp, *we, *be, *wn, *bn;
+  template <typename T>
+  __device__ __forceinline__ DView<const T> xview() const {
+    return DView<const T>{static_cast<const T*>(x), 0, 0, 0, 0, xcs};
+  }
+  template <typename T>
+  __device__ __forceinline__ DView<T> yview() const {
+    return DView<T>{static_cast<T*>(y), 0, 0, 0, 0, ycs};
+  }
+};
+struct Hg3Sides {
+  Hg3Side s[2];  // indexed by blockIdx.z (uniform per workgroup: scalar loads from the kernel arguments)
+};
+
 // ---- 1. context [mean_N X | max_N X] and the prototypes
 template <typename T, int D, int E>
-__global__ __launch_bounds__(256) void hg3_ctx_kernel(DView<const T> x, int N, unsigned char* __restrict__ ws, Hg3Ws o) {
+__global__ __launch_bounds__(256) void hg3_ctx_kernel(Hg3Sides p, int N, Hg3Ws o) {
   using C = Hg3<T, D, E>;
   constexpr int V = C::V, CV = C::CV, TL = C::TL;
   __shared__ float s_red[4 * 2 * D];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int sl = blockIdx.x, b = blockIdx.y, NS = gridDim.x;
   const int cv = tid % CV, tl = tid / CV;
+  const Hg3Side& sd = p.s[blockIdx.z];
+  const DView<const T> x = sd.xview<T>();
+  unsigned char* __restrict__ ws = sd.ws;
   const T* xb = x.p + (int64_t)b * N * x.cs;
   const int n0 = sl * HG3_TS, n1 = min(N, n0 + HG3_TS);
   float sm[V], mx[V];
@@ -98,9 +126,13 @@ __global__ __launch_bounds__(256) void hg3_ctx_kernel(DView<const T> x, int N, u
 // ctx + bc): 16 rows per workgroup, 4 per wave, every row's weights loaded in one round trip together with the
 // partials (lane l holds k = l*KL .. +KL-1), reduced across the wave
 template <int D, int E>
-__global__ __launch_bounds__(256) void hg3_proto_kernel(int N, int NS, const unsigned char* __restrict__ ws, Hg3Ws o,
-                                                        const float* __restrict__ base, const float* __restrict__ wc,
-                                                        const float* __restrict__ bc, unsigned char* __restrict__ wsw) {
+__global__ __launch_bounds__(256) void hg3_proto_kernel(Hg3Sides p, int N, int NS, Hg3Ws o) {
+  const Hg3Side& sd = p.s[blockIdx.z];
+  const unsigned char* __restrict__ ws = sd.ws;
+  unsigned char* __restrict__ wsw = sd.ws;
+  const float* __restrict__ base = sd.base;
+  const float* __restrict__ wc = sd.wc;
+  const float* __restrict__ bc = sd.bc;
   constexpr int KL = 2 * D / 64;  // ctx entries per lane (2 or 4)
   constexpr int C4 = 2 * D / 4;   // f32x4 columns of a slice partial
   constexpr int ZG = 256 / C4;    // slice groups
@@ -154,10 +186,12 @@ __global__ __launch_bounds__(256) void hg3_proto_kernel(int N, int NS, const uns
 
 // ---- 2. logits, online-softmax partials, He = A^T X, He2, He3
 template <typename T, int D, int E>
-__global__ __launch_bounds__(256) void hg3_edge_kernel(DView<const T> x, int N, int H, unsigned char* __restrict__ ws,
-                                                       Hg3Ws o, const T* __restrict__ wp, const float* __restrict__ bp,
-                                                       const float* __restrict__ we, const float* __restrict__ be,
-                                                       const float* __restrict__ wn) {
+__global__ __launch_bounds__(256) void hg3_edge_kernel(Hg3Sides p, int N, int H, Hg3Ws o) {
+  const Hg3Side& sd = p.s[blockIdx.z];
+  const DView<const T> x = sd.xview<T>();
+  unsigned char* __restrict__ ws = sd.ws;
+  const T* __restrict__ wp = static_cast<const T*>(sd.wp);
+  const float* __restrict__ bp = sd.bp;
   using C = Hg3<T, D, E>;
   constexpr int V = C::V, CV = C::CV, TL = C::TL, NTC = C::NTC, KS = C::KS, R2 = C::R2;
   using vec = typename Vec<T>::type;
@@ -296,9 +330,12 @@ __global__ __launch_bounds__(256) void hg3_edge_kernel(DView<const T> x, int N, 
 // He3[e] = Wn He2[e] (row e of each product depends on row e only).  Every load is issued before the first use:
 // a thread's two weight rows (output d = tid % D), the slices' (max, sum) of e, this thread's He' entries.
 template <int D, int E>
-__global__ __launch_bounds__(256) void hg3_merge_kernel(int NS, unsigned char* __restrict__ ws, Hg3Ws o,
-                                                        const float* __restrict__ we, const float* __restrict__ be,
-                                                        const float* __restrict__ wn) {
+__global__ __launch_bounds__(256) void hg3_merge_kernel(Hg3Sides p, int NS, Hg3Ws o) {
+  const Hg3Side& sd = p.s[blockIdx.z];
+  unsigned char* __restrict__ ws = sd.ws;
+  const float* __restrict__ we = sd.we;
+  const float* __restrict__ be = sd.be;
+  const float* __restrict__ wn = sd.wn;
   constexpr int R2 = (2 * E + E * D + 3) / 4 * 4;
   constexpr int ZG = 256 / D;  // slice groups of the He' merge (4 at D 64, 2 at D 128)
   constexpr int ZB = (HG3_NSMAX + ZG - 1) / ZG;
@@ -382,9 +419,12 @@ __global__ __launch_bounds__(256) void hg3_merge_kernel(int NS, unsigned char* _
 
 // ---- 3. y = GELU(A He3 + bn) + X, A = exp(l - m) / S
 template <typename T, int D, int E>
-__global__ __launch_bounds__(256) void hg3_out_kernel(DView<const T> x, DView<T> y, int N,
-                                                      const unsigned char* __restrict__ ws, Hg3Ws o,
-                                                      const float* __restrict__ bn) {
+__global__ __launch_bounds__(256) void hg3_out_kernel(Hg3Sides p, int N, Hg3Ws o) {
+  const Hg3Side& sd = p.s[blockIdx.z];
+  const DView<const T> x = sd.xview<T>();
+  const DView<T> y = sd.yview<T>();
+  const unsigned char* __restrict__ ws = sd.ws;
+  const float* __restrict__ bn = sd.bn;
   using C = Hg3<T, D, E>;
   constexpr int V = C::V, CV = C::CV, TL = C::TL;
   const int tid = threadIdx.x, cv = tid % CV, tl = tid / CV;
@@ -418,20 +458,25 @@ __global__ __launch_bounds__(256) void hg3_out_kernel(DView<const T> x, DView<T>
   }
 }
 
+static Hg3Side hg3_side(const ydbl_hg_desc* d) {
+  return Hg3Side{d->x.ptr, d->y.ptr, d->x.cs, d->y.cs, reinterpret_cast<unsigned char*>(d->workspace),
+                 d->proto_base, d->ctx_w, d->ctx_b, d->pre_w, d->pre_b, d->edge_w, d->edge_b, d->node_w, d->node_b};
+}
+
+// d1 == nullptr: the single call (gridDim.z = 1); else both calls' workgroups in each of the five launches
 template <typename T, int D, int E>
-static int hgf_go(const ydbl_hg_desc* d, hipStream_t s) {
+static int hgf_go(const ydbl_hg_desc* d, const ydbl_hg_desc* d1, hipStream_t s) {
   const int N = d->x.h * d->x.w, B = d->x.n;
   const int NS = (N + HG3_TS - 1) / HG3_TS;
   const Hg3Ws o = hg3_ws(B, N, D, E);
-  unsigned char* ws = reinterpret_cast<unsigned char*>(d->workspace);
-  const DView<const T> xv{reinterpret_cast<const T*>(d->x.ptr), d->x.n, d->x.h, d->x.w, d->x.c, d->x.cs};
-  hg3_ctx_kernel<T, D, E><<<dim3(NS, B), 256, 0, s>>>(xv, N, ws, o);
-  hg3_proto_kernel<D, E><<<dim3(E * D / 16, B), 256, 0, s>>>(N, NS, ws, o, d->proto_base, d->ctx_w, d->ctx_b, ws);
-  hg3_edge_kernel<T, D, E><<<dim3(NS, B), 256, 0, s>>>(xv, N, d->num_heads, ws, o, reinterpret_cast<const T*>(d->pre_w),
-                                                       d->pre_b, d->edge_w, d->edge_b, d->node_w);
-  hg3_merge_kernel<D, E><<<dim3(E, B), 256, 0, s>>>(NS, ws, o, d->edge_w, d->edge_b, d->node_w);
-  hg3_out_kernel<T, D, E><<<dim3(NS, B), 256, 0, s>>>(xv, dview<T>(d->y), N, ws, o, d->node_b);
-  return check_launch("ydbl_hg_fused");
+  const Hg3Sides p{{hg3_side(d), hg3_side(d1 ? d1 : d)}};
+  const unsigned Z = d1 ? 2 : 1;
+  hg3_ctx_kernel<T, D, E><<<dim3(NS, B, Z), 256, 0, s>>>(p, N, o);
+  hg3_proto_kernel<D, E><<<dim3(E * D / 16, B, Z), 256, 0, s>>>(p, N, NS, o);
+  hg3_edge_kernel<T, D, E><<<dim3(NS, B, Z), 256, 0, s>>>(p, N, d->num_heads, o);
+  hg3_merge_kernel<D, E><<<dim3(E, B, Z), 256, 0, s>>>(p, NS, o);
+  hg3_out_kernel<T, D, E><<<dim3(NS, B, Z), 256, 0, s>>>(p, N, o);
+  return check_launch(d1 ? "ydbl_hg_fused_pair" : "ydbl_hg_fused");
 }
 
 template <typename F>
@@ -459,8 +504,7 @@ extern "C" int64_t ydbl_hg_fused_workspace(int32_t n, int32_t tokens, int32_t di
   return hg3_ws(n, tokens, dim, edges).total;
 }
 
-extern "C" int ydbl_hg_fused(const ydbl_hg_desc* d, void* stream) {
-  if (!d) return fail(YDBL_EINVAL, "hg_fused: null descriptor");
+static int hgf_check(const ydbl_hg_desc* d) {
   if (check_view(&d->x, "hg_fused.x", true) || check_view(&d->y, "hg_fused.y", true)) return YDBL_EINVAL;
   if (d->y.c != d->x.c || d->y.n != d->x.n || d->y.h * d->y.w != d->x.h * d->x.w || d->y.dtype != d->x.dtype)
     return fail(YDBL_EINVAL, "hg_fused: y shape mismatch");
@@ -471,8 +515,52 @@ extern "C" int ydbl_hg_fused(const ydbl_hg_desc* d, void* stream) {
   if (d->num_heads < 1 || d->x.c != 16 * d->num_heads) return fail(YDBL_EINVAL, "hg_fused: head_dim must be 16");
   if (ydbl_hg_fused_workspace(d->x.n, d->x.h * d->x.w, d->x.c, d->num_edges, d->x.dtype) < 0)
     return fail(YDBL_EINVAL, "hg_fused: (dim, edges) must be (64|128, 4|8)");
+  return YDBL_OK;
+}
+
+static int hgf_launch(const ydbl_hg_desc* d, const ydbl_hg_desc* d1, void* stream) {
   hipStream_t s = as_stream(stream);
   return hgf_dispatch(d->x.c, d->num_edges, d->x.dtype == YDBL_F16, [&](auto T0, auto D0, auto E0) -> int {
-    return hgf_go<decltype(T0), decltype(D0)::value, decltype(E0)::value>(d, s);
+    return hgf_go<decltype(T0), decltype(D0)::value, decltype(E0)::value>(d, d1, s);
   });
+}
+
+extern "C" int ydbl_hg_fused(const ydbl_hg_desc* d, void* stream) {
+  if (!d) return fail(YDBL_EINVAL, "hg_fused: null descriptor");
+  if (const int r = hgf_check(d)) return r;
+  return hgf_launch(d, nullptr, stream);
+}
+
+// Do two channel-strided views share an element?  Views whose byte extents intersect count as overlapping unless
+// they are channel slices of one buffer (same pixel stride) with disjoint channel ranges.
+static bool hgf_views_overlap(const ydbl_view& a, const ydbl_view& b) {
+  const int64_t es = a.dtype == YDBL_F16 ? 2 : 4;
+  const auto pa = reinterpret_cast<uintptr_t>(a.ptr), pb = reinterpret_cast<uintptr_t>(b.ptr);
+  const uintptr_t ea = pa + (((int64_t)a.n * a.h * a.w - 1) * a.cs + a.c) * es;
+  const uintptr_t eb = pb + (((int64_t)b.n * b.h * b.w - 1) * b.cs + b.c) * es;
+  if (ea <= pb || eb <= pa) return false;
+  if (a.cs != b.cs || a.dtype != b.dtype) return true;
+  const int64_t row = (int64_t)a.cs * es;
+  const int64_t r = pb >= pa ? int64_t((pb - pa) % row) : int64_t((row - int64_t((pa - pb) % row)) % row);
+  return !(r >= a.c * es && r + b.c * es <= row);  // b's channels start r bytes after a's within a pixel
+}
+
+extern "C" int ydbl_hg_fused_pair(const ydbl_hg_desc* d0, const ydbl_hg_desc* d1, void* stream) {
+  if (!d0 || !d1) return fail(YDBL_EINVAL, "hg_fused_pair: null descriptor");
+  bool pair = !hgf_check(d0) && !hgf_check(d1);
+  pair = pair && d0->x.n == d1->x.n && d0->x.h * d0->x.w == d1->x.h * d1->x.w && d0->x.c == d1->x.c &&
+         d0->num_edges == d1->num_edges && d0->num_heads == d1->num_heads && d0->x.dtype == d1->x.dtype;
+  // one side's output may be neither the other's input nor its output, and the workspaces are two
+  pair = pair && !hgf_views_overlap(d0->y, d1->x) && !hgf_views_overlap(d0->y, d1->y) &&
+         !hgf_views_overlap(d1->y, d0->x);
+  if (pair) {
+    const int64_t nws = hg3_ws(d0->x.n, d0->x.h * d0->x.w, d0->x.c, d0->num_edges).total;
+    const auto w0 = reinterpret_cast<uintptr_t>(d0->workspace), w1 = reinterpret_cast<uintptr_t>(d1->workspace);
+    pair = w0 + nws <= w1 || w1 + nws <= w0;
+  }
+  if (!pair) {  // not two independent calls of one shape: the two calls in order
+    const int r = ydbl_hg_fused(d0, stream);
+    return r ? r : ydbl_hg_fused(d1, stream);
+  }
+  return hgf_launch(d0, d1, stream);
 }

@@ -936,25 +936,41 @@ class AdaHGConv(PlanModule):
         self.edge_proj = nn.Sequential(nn.Linear(embed_dim, embed_dim), nn.GELU())
         self.node_proj = nn.Sequential(nn.Linear(embed_dim, embed_dim), nn.GELU())
 
+    def _params(self, plan):
+        g, c = self.edge_generator, plan.const
+        return [c(g.prototype_base.float()), c(g.context_net.weight.float()), c(g.context_net.bias.float()),
+                c(self.edge_proj[0].weight.float()), c(self.edge_proj[0].bias.float()),
+                c(self.node_proj[0].weight.float()), c(self.node_proj[0].bias.float())]
+
+    def fused_desc(self, plan, x, y, p=None):
+        """(HgDesc, keep-list) of the one-call route (ydbl_hg_fused / ydbl_hg_fused_pair), or None where the
+        staged route has to run: YDBL_HG_UNFUSED, a head_dim other than 16, a (dim, edges, tokens) the fused
+        kernels do not take, or y intersecting x."""
+        g = self.edge_generator
+        D, E = x.c, g.num_hyperedges
+        nws = _lib.lib.ydbl_hg_fused_workspace(x.n, x.h * x.w, D, E, _lib.dtype_code(plan.dtype))
+        if (os.environ.get("YDBL_HG_UNFUSED") or D != 16 * g.num_heads or nws <= 0
+                or not (y.base is not x.base or y.off + y.c <= x.off or x.off + x.c <= y.off)):
+            return None
+        p = self._params(plan) if p is None else p
+        c = plan.const
+        pw = c(g.pre_head_proj.weight.detach().float().to(plan.dtype).contiguous())
+        pb = c(g.pre_head_proj.bias.detach().float())
+        ws = plan.scratch(nws)  # per-slice partials, fully written before they are read
+        d = HgDesc(x.struct(), _null_view(), y.struct(), E, g.num_heads, *[t.data_ptr() for t in p], ws.data_ptr(),
+                   pw.data_ptr(), pb.data_ptr())
+        return d, [d, pw, pb, ws, *p]
+
     def emit(self, plan, x, out=None):
         g = self.edge_generator
         D, E = x.c, g.num_hyperedges
         y = out if out is not None else plan.alloc(x.n, x.h, x.w, D)
-        c = plan.const
-        p = [c(g.prototype_base.float()), c(g.context_net.weight.float()), c(g.context_net.bias.float()),
-             c(self.edge_proj[0].weight.float()), c(self.edge_proj[0].bias.float()),
-             c(self.node_proj[0].weight.float()), c(self.node_proj[0].bias.float())]
-        nws = _lib.lib.ydbl_hg_fused_workspace(x.n, x.h * x.w, D, E, _lib.dtype_code(plan.dtype))
-        if (not os.environ.get("YDBL_HG_UNFUSED") and D == 16 * g.num_heads and nws > 0
-                and x.c == D and (y.base is not x.base or y.off + y.c <= x.off or x.off + x.c <= y.off)):
-            # the whole AdaHGConv, pre_head_proj included, from one C-ABI call (csrc/hg_fused.hip: three kernels
-            # over (token slice, image) workgroups)
-            pw = c(g.pre_head_proj.weight.detach().float().to(plan.dtype).contiguous())
-            pb = c(g.pre_head_proj.bias.detach().float())
-            ws = plan.scratch(nws)  # per-slice partials, fully written before they are read
-            d = HgDesc(x.struct(), _null_view(), y.struct(), E, g.num_heads, *[t.data_ptr() for t in p], ws.data_ptr(),
-                       pw.data_ptr(), pb.data_ptr())
-            plan.launch("ydbl_hg_fused", d, what="AdaHG.fused", keep=[d, pw, pb, ws, *p])
+        p = self._params(plan)
+        fused = self.fused_desc(plan, x, y, p)
+        if fused is not None:
+            # the whole AdaHGConv, pre_head_proj included, from one C-ABI call (csrc/hg_fused.hip: five kernels
+            # over (token slice, image) and (hyperedge, image) workgroups)
+            plan.launch("ydbl_hg_fused", fused[0], what="AdaHG.fused", keep=fused[1])
             return y
         # X_proj = pre_head_proj(X) as a 1x1 conv over the token grid
         xp = plan.alloc(x.n, x.h, x.w, D)
@@ -1065,14 +1081,25 @@ class HyperACE(PlanModule):
         """Both C3AH branches read y1 (block.py:1886-1895): their four input 1x1s (cv1, cv2 of each) run as ONE
         launch into one buffer laid out [b2.m | b2.cv2 | b2.cv1 | b1.cv1 | b1.cv2 | b1.m], so each branch's
         cv3 input is contiguous: b2's in the reference order cat(m, cv2), b1's as (cv2, m) with cv3's weight
-        columns swapped to match (the same sums, in another order of K)."""
+        columns swapped to match (the same sums, in another order of K).  The two AdaHGConvs are independent
+        (disjoint slices of bb), so where both take the one-call route they share its five launches
+        (ydbl_hg_fused_pair); YDBL_NO_HG_PAIR=1 keeps a call per branch."""
         b1, b2 = self.branch1, self.branch2
         c_ = b1.cv1.conv.out_channels
         bb = plan.alloc(y1.n, y1.h, y1.w, 6 * c_)
         emit_merged(plan, [b2.cv2, b2.cv1, b1.cv1, b1.cv2], y1, bb.cslice(c_, 4 * c_), what="C3AHx2.cv1|cv2")
-        b2.m.emit(plan, bb.cslice(2 * c_, c_), bb.cslice(0, c_))
-        b2.cv3.emit(plan, bb.cslice(0, 2 * c_), out2)
-        b1.m.emit(plan, bb.cslice(3 * c_, c_), bb.cslice(5 * c_, c_))
+        x2, m2, x1, m1 = bb.cslice(2 * c_, c_), bb.cslice(0, c_), bb.cslice(3 * c_, c_), bb.cslice(5 * c_, c_)
+        f2 = f1 = None
+        if not os.environ.get("YDBL_NO_HG_PAIR"):
+            f2 = b2.m.hgnn.fused_desc(plan, x2, m2)
+            f1 = b1.m.hgnn.fused_desc(plan, x1, m1) if f2 is not None else None
+        if f1 is not None:
+            plan.launch("ydbl_hg_fused_pair", f2[0], f1[0], what="AdaHG.fused2", keep=[*f2[1], *f1[1]])
+            b2.cv3.emit(plan, bb.cslice(0, 2 * c_), out2)
+        else:
+            b2.m.emit(plan, x2, m2)
+            b2.cv3.emit(plan, bb.cslice(0, 2 * c_), out2)
+            b1.m.emit(plan, x1, m1)
         w, b = b1.cv3.folded()
         w = torch.cat([w[:, c_:], w[:, :c_]], 1)
         emit_conv2d(plan, b1.cv3.conv, bb.cslice(4 * c_, 2 * c_), out1, w, b, _act_code(b1.cv3.act), what="Conv1x1")
