@@ -65,6 +65,8 @@
  *                             DetectionValidator.update_metrics models/yolo/detect/val.py:140-159
  *   ydbl_global_avgpool    <- BaseModel._predict_once with embed set, nn/tasks.py:168-169
  *                             (adaptive_avg_pool2d(x, (1, 1)).squeeze(-1).squeeze(-1) of a layer's output)
+ *   ydbl_bytetrack_update  <- BYTETracker.update trackers/byte_tracker.py:293-405 as driven per image by
+ *                             on_predict_postprocess_end trackers/track.py:53-87
  */
 #ifndef YDBL_H
 #define YDBL_H
@@ -619,6 +621,53 @@ typedef struct {
 } ydbl_avgpool_desc;
 int64_t ydbl_global_avgpool_workspace(const ydbl_avgpool_desc* d);
 int ydbl_global_avgpool(const ydbl_avgpool_desc* d, void* stream);
+
+/* ByteTrack association of a batch of NMS outputs, on the device (BYTETracker.update trackers/byte_tracker.py:293-405
+ * with STrack :51-228, KalmanFilterXYAH trackers/utils/kalman_filter.py:52-236, iou_distance / fuse_score /
+ * linear_assignment trackers/utils/matching.py:20-157, and the per-image driver trackers/track.py:53-87).
+ * det fp32 rows x1,y1,x2,y2,conf,cls and det_count int32 as ydbl_nms writes them; det_stride / count_stride (0 =
+ * dense): floats between the images of det (>= max_det * 6) and int32s between the images of det_count, so the
+ * records of ydbl_nms_desc (out_stride / count_stride) are read in place.  A count above max_det is clamped.
+ * hw fp32 [n][2]: each image's (height, width), the extents the output boxes are clipped to.
+ * One workgroup per tracker.  trackers == 1: the n images go through ONE tracker in row order, as consecutive frames
+ * (the reference for every non-stream source); trackers == n: image i is the next frame of tracker i.  Anything else
+ * is YDBL_EINVAL.  reset_each != 0: the tracker is reset before every image (persist=False).
+ * Per image: out fp32 [n][max_det][7] rows x1,y1,x2,y2,id,conf,cls = the activated tracked tracks in the reference's
+ * list order, clipped (rows past the count zeroed); out_count int32 [n]; tracked int32 [n] = 1 when rows were
+ * written, 0 = "leave this image's predicted boxes as they are" (no detection: update() is not called and the
+ * frame counter stays; or update() returned no track); out_idx int32 [n][max_det] or NULL: each row's detection
+ * index (-1 past the count).
+ * state: trackers * ydbl_bytetrack_state_bytes(max_tracks, max_det) bytes, 16-byte aligned, caller-owned, zeroed by
+ * the caller: a zeroed state is a reset tracker.  Per tracker: int64 sequence counter | int32 frame_id, next id
+ * (ids issued so far), overflow, slot high-water mark, 2 x pad | per slot mean[8] and cov[8][8] fp64, an int64
+ * sequence key (list order), state, is_activated, id, frame_id, start_frame, tracklet_len, idx, removed-list
+ * membership, score, cls.  More than max_tracks live tracks (tracked + lost + unconfirmed): no track is started for
+ * that detection, no id is spent and `overflow` is incremented; nothing is overwritten.
+ * Kalman arithmetic fp64, IoU and fused cost fp32 in numpy's operation order, score comparisons fp32.  The
+ * assignment is exact: an optimum of sum_matched (c_ij - thresh) over the pairs with c_ij <= thresh (what
+ * lap.lapjv(extend_cost=True, cost_limit=thresh) minimises), by shortest augmenting paths in fp64; where the optimum
+ * is not unique the choice is unspecified.  Detections with a non-finite box, score or class, or of zero height,
+ * take no part (never matched, never a new track).  The reference's removed_stracks list is kept as a per-slot
+ * flag and is not cut at 1000 entries.  No allocation, no host sync, graph-capturable.
+ * YDBL_EINVAL: null descriptor / pointer, n, max_det or max_tracks < 1, trackers not in {1, n}, a threshold outside
+ * [0, 1], a stride too small, state too small or misaligned; YDBL_ECAPACITY: max_tracks and max_det together need
+ * more than the 160 KiB of LDS of a workgroup (512 and 300 need 61 KiB). */
+typedef struct {
+  const float* det; const int32_t* det_count;
+  int32_t n, max_det;
+  int64_t det_stride, count_stride;
+  const float* hw;
+  double track_high_thresh, track_low_thresh, new_track_thresh, match_thresh;
+  int32_t fuse_score, track_buffer;
+  int32_t max_time_lost;   /* int(frame_rate / 30 * track_buffer), frame_rate 30 */
+  int32_t max_tracks;
+  int32_t trackers, reset_each;
+  float* out; int32_t* out_count; int32_t* tracked; int32_t* out_idx;
+  void* state;
+  int64_t state_bytes;
+} ydbl_track_desc;
+int64_t ydbl_bytetrack_state_bytes(int32_t max_tracks, int32_t max_det); /* per tracker; -1: an argument < 1 */
+int ydbl_bytetrack_update(const ydbl_track_desc* d, void* stream);
 
 const char* ydbl_last_error(void);
 const char* ydbl_version(void);

@@ -166,6 +166,17 @@ class AvgPoolDesc(C.Structure):
                 ("workspace_bytes", C.c_int64)]
 
 
+class TrackDesc(C.Structure):
+    """ydbl_track_desc: ByteTrack association over the det | count records of ydbl_nms (Model.track)."""
+    _fields_ = [("det", C.c_void_p), ("det_count", C.c_void_p), ("n", C.c_int32), ("max_det", C.c_int32),
+                ("det_stride", C.c_int64), ("count_stride", C.c_int64), ("hw", C.c_void_p),
+                ("track_high_thresh", C.c_double), ("track_low_thresh", C.c_double),
+                ("new_track_thresh", C.c_double), ("match_thresh", C.c_double), ("fuse_score", C.c_int32),
+                ("track_buffer", C.c_int32), ("max_time_lost", C.c_int32), ("max_tracks", C.c_int32),
+                ("trackers", C.c_int32), ("reset_each", C.c_int32), ("out", C.c_void_p), ("out_count", C.c_void_p),
+                ("tracked", C.c_void_p), ("out_idx", C.c_void_p), ("state", C.c_void_p), ("state_bytes", C.c_int64)]
+
+
 # name -> (argtypes, restype); every entry must exist in include/ydbl.h
 _P = C.c_void_p
 _VP = C.POINTER(View)
@@ -223,6 +234,8 @@ SIGNATURES = {
     "ydbl_confusion_matrix": ([C.POINTER(ConfusionDesc), _P], C.c_int),
     "ydbl_global_avgpool_workspace": ([C.POINTER(AvgPoolDesc)], C.c_int64),
     "ydbl_global_avgpool": ([C.POINTER(AvgPoolDesc), _P], C.c_int),
+    "ydbl_bytetrack_state_bytes": ([C.c_int32, C.c_int32], C.c_int64),
+    "ydbl_bytetrack_update": ([C.POINTER(TrackDesc), _P], C.c_int),
     "ydbl_last_error": ([], C.c_char_p),
     "ydbl_version": ([], C.c_char_p),
 }

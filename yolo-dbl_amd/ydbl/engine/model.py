@@ -1,4 +1,4 @@
-"""User API: ``YOLO(cfg_or_weights)`` with ``.predict()``, ``.val()``, ``.fuse()``.
+"""User API: ``YOLO(cfg_or_weights)`` with ``.predict()``, ``.track()``, ``.embed()``, ``.val()``, ``.fuse()``.
 
 Mirrors U/engine/model.py:84-643 and U/models/yolo/model.py:52-100 for the
 detect task: model files named like the reference's
@@ -175,6 +175,7 @@ class Model:
         self.ckpt_path = None
         self.verbose = verbose
         self._sessions = OrderedDict()  # LRU of compiled sessions (each holds its own HBM buffers)
+        self._trackers = {}  # track(persist=True): the device state of the ByteTrack trackers (engine.tracker)
         model = str(model)
         suffix = Path(model).suffix.lower()
         if suffix in (".pt", ".pth"):
@@ -494,6 +495,154 @@ class Model:
         return iter(results) if stream else results
 
     __call__ = predict
+
+    # ------------------------------------------------------------------ tracking
+    def reset_trackers(self):
+        """Forget every tracker's identities (the next track() call starts at id 1).  Compiled sessions stay."""
+        self._trackers.clear()
+        return self
+
+    def _tracker_state(self, dev, cfg, max_det, track_rows, n, persist, max_tracks):
+        from .tracker import TrackerState, settings_key
+
+        trackers = n if track_rows == "parallel" else 1
+        key = (str(dev), settings_key(cfg), int(max_det), track_rows, trackers, int(max_tracks))
+        if not persist:
+            self._trackers.clear()
+        if track_rows == "parallel":
+            other = [k for k in self._trackers if k[3] == "parallel" and k[:3] == key[:3] and k[4] != trackers]
+            if other:
+                raise ValueError(f"track_rows='parallel': this call has {n} rows, the trackers were started with "
+                                 f"{other[0][4]}; keep the batch size, or call reset_trackers()")
+        ts = self._trackers.get(key)
+        if ts is None:
+            with torch.cuda.device(dev):
+                ts = self._trackers[key] = TrackerState(cfg, dev, max_det, trackers, max_tracks)
+        return ts
+
+    def track(self, source=None, stream=False, persist=False, tracker="bytetrack.yaml", track_rows="sequence",
+              **kwargs):
+        """U/engine/model.py:562-607 + U/trackers/track.py:18-87: predict() (conf defaults to 0.1, batch to 1) followed
+        by ByteTrack, on the device: the association kernel (ydbl_bytetrack_update) runs behind the NMS on the same
+        stream and reads its det | count where they lie.  Every source kind of predict() is accepted.  Results whose
+        image got tracks carry 7-column boxes ``x1, y1, x2, y2, id, conf, cls`` (``boxes.id``, ``boxes.is_track``),
+        the others keep their predicted 6 columns (``boxes.id`` None), as in the reference.
+
+        The images of a call go through ONE tracker in row order, as consecutive frames.  persist=False resets the
+        tracker before every image; persist=True keeps the identities on the model across calls (reset_trackers()
+        drops them; reset_sessions() and load() do not: weights do not invalidate identities).
+
+        tracker: ``bytetrack.yaml`` (the built-in settings), a path to a YAML of the reference's layout, or a dict.
+        Unlike the reference, whose default is ``botsort.yaml``, the default here is ByteTrack, the one tracker
+        implemented (``tracker_type: botsort`` raises NotImplementedError).
+
+        track_rows="parallel" (an extension; needs persist=True and the same batch size on every call): row i of
+        every call is camera i's next frame, through n independent trackers.  Ids are per tracker, each counted from
+        1 (the reference's id counter is one class variable shared by all trackers).
+
+        max_tracks (default 512): the live tracks one tracker holds; a detection that cannot start a track for lack
+        of room raises RuntimeError when the batch's results are first looked at.  embed is refused (ValueError);
+        fp8 and augment=True only change the detector.  For tensor sources nothing synchronises: the boxes are
+        chosen (7 or 6 columns per image) on first access, with one sync for the batch."""
+        from .sources import check_path_source, file_batches, frames_from_images, is_frame_source
+        from .tracker import MAX_TRACKS, check_track_args, load_settings
+
+        kwargs.setdefault("conf", 0.1)
+        kwargs.setdefault("batch", 1)
+        max_tracks = int(kwargs.pop("max_tracks", MAX_TRACKS))
+        args = {**DEFAULTS, **self.overrides, **kwargs}
+        check_track_args(args["embed"], track_rows, persist)
+        cfg = load_settings(tracker)
+        if max_tracks < 1:
+            raise ValueError(f"max_tracks must be >= 1, got {max_tracks}")
+        check_augment(args["augment"], args["fp8"])
+        if source is None:
+            raise ValueError("track() needs a source (no default asset is bundled)")
+        is_tensor = isinstance(source, torch.Tensor) or (isinstance(source, (list, tuple)) and source
+                                                         and isinstance(source[0], torch.Tensor))
+        if not is_tensor and not check_path_source(source) and not is_frame_source(source):
+            raise TypeError(f"unsupported source type {type(source).__name__}")
+        dev = select_device(args["device"])
+        topt = (cfg, track_rows, persist, max_tracks)
+        if not persist:
+            self._trackers.clear()
+        if is_tensor:
+            res = self._track_tensor(source, args, dev, topt)
+            return iter(res) if stream else res
+        if check_path_source(source):
+            gen = (r for paths, frames in file_batches(source, args["batch"])
+                   for r in self._track_frames(frames, args, dev, topt, paths))
+            return gen if stream else list(gen)
+        paths, frames = frames_from_images(source)
+        res = self._track_frames(frames, args, dev, topt, paths)
+        return iter(res) if stream else res
+
+    def _track_tensor(self, source, args, dev, topt):
+        from .tracker import LazyTracks
+
+        cfg, track_rows, persist, max_tracks = topt
+        t0 = time.perf_counter()
+        im = check_tensor_source(source, int(self.model.stride.max()))
+        if im.device != dev:
+            im = load_tensor_source(im).to(dev, non_blocking=True).float()
+        b, _, h, w = im.shape
+        kw = dict(half=args["half"], conf=args["conf"], iou=args["iou"], max_det=args["max_det"],
+                  agnostic=args["agnostic_nms"], classes=args["classes"], device=dev, fp8=args["fp8"],
+                  streams=args["streams"], fp8_calibration=args["fp8_calibration"], augment=args["augment"])
+        ts = self._tracker_state(dev, cfg, args["max_det"], track_rows, b, persist, max_tracks)
+        s = self.session(b, h, w, **kw)
+        t1 = time.perf_counter()
+        one, inv = _scale_consts(dev)
+        thr = 1.0 + (torch.finfo(im.dtype).eps if im.is_floating_point() else 0.0)
+        scale = torch.where(im.amax() > thr, inv, one)
+        det, cnt = s(im, scale)  # the session's copy path; the in-place binding is not needed here
+        if self._stale(s):
+            s = self.session(b, h, w, **kw)
+            det, cnt = s(im, scale)
+        # the tracker reads the session's det | count in place, on the stream that wrote them; then one copy of them
+        # for the images that keep their predicted boxes (the session's buffers are reused by the next call)
+        out, oc, tr = ts.update(det, cnt, [(h, w)] * b, reset_each=not persist)
+        dets, counts = det.clone(), cnt.clone()
+        t2 = time.perf_counter()
+        speed = {"preprocess": (t1 - t0) * 1e3 / b, "inference": (t2 - t1) * 1e3 / b, "postprocess": 0.0}
+        lazy = LazyTracks(ts, out, oc, tr, dets, counts)
+        hwc = _LazyHWC(im, scale)
+        names = self.model.names
+        return [Results(lambda i=i: hwc[i], path=f"image{i}.jpg", names=names, speed=speed, orig_shape=(h, w),
+                        boxes=lambda i=i: lazy[i]) for i in range(b)]
+
+    def _track_frames(self, frames, args, dev, topt, paths=None):
+        from .preprocess import letterbox_batch, scale_boxes
+        from .tracker import LazyTracks
+
+        cfg, track_rows, persist, max_tracks = topt
+        t0 = time.perf_counter()
+        frames = [frames] if isinstance(frames, np.ndarray) and frames.ndim == 3 else list(frames)
+        imgsz = args["imgsz"]
+        imgsz = (imgsz, imgsz) if isinstance(imgsz, int) else tuple(imgsz)
+        im = letterbox_batch(frames, imgsz, stride=int(self.model.stride.max()), device=dev)
+        b, _, h, w = im.shape
+        kw = dict(half=args["half"], conf=args["conf"], iou=args["iou"], max_det=args["max_det"],
+                  agnostic=args["agnostic_nms"], classes=args["classes"], device=dev, fp8=args["fp8"], clip=False,
+                  streams=args["streams"], fp8_calibration=args["fp8_calibration"], augment=args["augment"])
+        ts = self._tracker_state(dev, cfg, args["max_det"], track_rows, b, persist, max_tracks)
+        s = self.session(b, h, w, **kw)
+        t1 = time.perf_counter()
+        det, cnt = s(im)
+        if self._stale(s):
+            det, cnt = self.session(b, h, w, **kw)(im)
+        # scale_boxes to each frame's own coordinates (rows past the count scale to garbage nobody reads), then the
+        # same kernel over them with the frame's shape as the clip extent
+        dets, counts = det.clone(), cnt.clone()
+        shapes = [tuple(f.shape[:2]) for f in frames]
+        for i, shp in enumerate(shapes):
+            scale_boxes((h, w), dets[i], shp)
+        out, oc, tr = ts.update(dets, counts, shapes, reset_each=not persist)
+        lazy = LazyTracks(ts, out, oc, tr, dets, counts)
+        t2 = time.perf_counter()
+        speed = {"preprocess": (t1 - t0) * 1e3 / b, "inference": (t2 - t1) * 1e3 / b, "postprocess": 0.0}
+        return [Results(f, path=paths[i] if paths else f"image{i}.jpg", names=self.model.names, speed=speed,
+                        boxes=lambda i=i: lazy[i]) for i, f in enumerate(frames)]
 
     def val(self, data=None, **kwargs):
         """Detection mAP (U/engine/model.py:609-643): ``data`` = a data YAML, a dataset folder, an image folder /

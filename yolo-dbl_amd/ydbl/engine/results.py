@@ -237,6 +237,8 @@ class Results:
                 draw.rectangle([x1, y1, x2, y2], outline=col, width=lw)
                 if labels:
                     name = self.names[c] if self.names else str(c)
+                    if len(row) == 7:  # U/engine/results.py:538-539
+                        name = f"id:{int(row[4])} {name}"
                     text = f"{name} {cf:.2f}" if conf else name
                     tb = draw.textbbox((x1, y1), text)
                     th = tb[3] - tb[1]
@@ -258,11 +260,13 @@ class Results:
             return out
         h, w = self.orig_shape
         for row in self.boxes.data.tolist():
-            x1, y1, x2, y2, conf, cls = row[:6]
+            (x1, y1, x2, y2), conf, cls = row[:4], row[-2], row[-1]  # xyxy, track id when tracking, conf, cls
             if normalize:
                 x1, x2, y1, y2 = x1 / w, x2 / w, y1 / h, y2 / h
             out.append({"name": self.names[int(cls)], "class": int(cls), "confidence": round(conf, decimals),
                         "box": {k: round(v, decimals) for k, v in zip(("x1", "y1", "x2", "y2"), (x1, y1, x2, y2))}})
+            if self.boxes.is_track:  # U/engine/results.py:803-804
+                out[-1]["track_id"] = int(row[-3])
         return out
 
     def verbose(self):
