@@ -63,6 +63,9 @@
  *                             engine/validator.py:222-262, non-scipy branch)
  *   ydbl_confusion_matrix  <- ConfusionMatrix.process_batch utils/metrics.py:326-382 and its call sites in
  *                             DetectionValidator.update_metrics models/yolo/detect/val.py:140-159
+ *   ydbl_coco_match        <- COCOeval.evaluateImg (the COCO detection protocol's per-image, per-category greedy
+ *                             matching) as DetectionValidator.eval_json reaches it,
+ *                             models/yolo/detect/val.py:297-337; no crowd labels
  *   ydbl_global_avgpool    <- BaseModel._predict_once with embed set, nn/tasks.py:168-169
  *                             (adaptive_avg_pool2d(x, (1, 1)).squeeze(-1).squeeze(-1) of a layer's output)
  *   ydbl_bytetrack_update  <- BYTETracker.update trackers/byte_tracker.py:293-405 as driven per image by
@@ -600,6 +603,52 @@ typedef struct {
 } ydbl_confusion_desc;
 int64_t ydbl_confusion_workspace(int32_t n, int32_t max_det, int32_t n_gt);
 int ydbl_confusion_matrix(const ydbl_confusion_desc* d, void* stream);
+
+/* COCO-protocol matching of a batch of NMS outputs against ground-truth labels: what COCOeval.evaluateImg computes
+ * per (image, category, area range), for every IoU threshold, without crowd labels.  det / det_count / gt_box /
+ * gt_cls / gt_ofs as in ydbl_match_desc; a class is truncated to int and belongs to no category outside [0, nc);
+ * single_cls: every detection and label is category 0.  iou_thrs fp64 [n_iou <= 16] and area_rng fp64 [n_area <= 8][2]
+ * are HOST arrays, read during the call.
+ * Boxes: x = x1, y = y1, w = x2 - x1, h = y2 - y1 after conversion to fp64; area = w * h; IoU, in fp64 without
+ * contraction: iw = min(dx+dw, gx+gw) - max(dx, gx), ih likewise, 0 if iw <= 0 or ih <= 0, else
+ * i = iw*ih, iou = i / (dw*dh + gw*gh - i).
+ * Per (image, category): the rows d < min(det_count, max_det) of that category ordered by score descending (ties in
+ * row order; a NaN score sorts last), cut to the first min(max_dets, max_det).  Per area range a = (a0, a1) and
+ * threshold t: a label is ignored when its area < a0 or > a1; the detections, in that order, each take the label not
+ * yet taken (for this a, t) with the largest IoU among those with iou >= min(t, 1 - 1e-10), a non-ignored label before
+ * any ignored one, on an exact IoU tie the label later in label order; a matched detection inherits the label's
+ * ignore flag, an unmatched one is ignored when its own area lies outside the range.
+ * Outputs, each word written once by a plain vector store (no atomics on global memory; deterministic):
+ *   dt_rank    int32 [n][max_det]          the row's position in its (image, category) list, or -1: a row past the
+ *                                          count, of no category, or beyond the cut;
+ *   dt_matched int32 [n][max_det][n_area]  bit t set: matched at iou_thrs[t] (0 where dt_rank is -1);
+ *   dt_ignored int32 [n][max_det][n_area]  bit t set: ignored at iou_thrs[t] (0 where dt_rank is -1);
+ *   gt_ignore  uint8 [n_gt][n_area]        the label's ignore flag (every label, whatever its class);
+ *   invalid    int32 [n]                   rows below the count whose class is outside [0, nc) (0 with single_cls).
+ * One launch: a workgroup per (category, image).  No allocation, no host sync, graph-capturable, reentrant.
+ * ydbl_coco_workspace: bytes of `workspace` (0 today: the state is in LDS, and workspace may then be NULL; -1 for a
+ * negative argument).  YDBL_EINVAL: null descriptor / pointer, n or max_det < 1, n > 65535, max_det > 2^20, nc outside
+ * [1, 32767], n_iou outside [1, 16], n_area outside [1, 8], max_dets outside [1, 1024], a NaN threshold, an area range
+ * with lo > hi.  YDBL_ECAPACITY: min(max_dets, max_det) detections and n_gt labels (all of which one image and category
+ * may own) need more than the 160 KiB of LDS of a workgroup: 36 bytes per detection, 48 per label (100 detections
+ * leave room for 3336 labels per batch).  Both are returned before any launch. */
+typedef struct {
+  const float* det; const int32_t* det_count;
+  int32_t n, max_det;
+  const float* gt_box; const float* gt_cls; const int32_t* gt_ofs;
+  int32_t n_gt;
+  int32_t single_cls;
+  int32_t nc;
+  const double* iou_thrs; int32_t n_iou;   /* host */
+  const double* area_rng; int32_t n_area;  /* host, [n_area][2] */
+  int32_t max_dets;                        /* the cut per (image, category): 100 */
+  int32_t* dt_rank; int32_t* dt_matched; int32_t* dt_ignored;
+  uint8_t* gt_ignore;
+  int32_t* invalid;
+  void* workspace; /* ydbl_coco_workspace(n, max_det, n_gt, nc) bytes */
+} ydbl_coco_desc;
+int64_t ydbl_coco_workspace(int32_t n, int32_t max_det, int32_t n_gt, int32_t nc);
+int ydbl_coco_match(const ydbl_coco_desc* d, void* stream);
 
 /* Global average pool of an NHWC view: y[n][c] = mean over (h, w) of x[n][.][.][c], the pooled layer feature of
  * BaseModel._predict_once with embed set (nn/tasks.py:168-169: adaptive_avg_pool2d(x, (1, 1)).squeeze(-1).squeeze(-1)).

@@ -34,4 +34,4 @@ int check_view(const ydbl_view* v, const char* name, bool need_vec_align) {
 }  // namespace ydbl
 
 extern "C" const char* ydbl_last_error(void) { return ydbl::g_last_error.c_str(); }
-extern "C" const char* ydbl_version(void) { return "ydbl 0.4 gfx950"; }
+extern "C" const char* ydbl_version(void) { return "ydbl 0.5 gfx950"; }

@@ -155,6 +155,17 @@ class ConfusionDesc(C.Structure):
                 ("invalid", C.c_void_p), ("workspace", C.c_void_p)]
 
 
+class CocoDesc(C.Structure):
+    """ydbl_coco_desc: COCO-protocol matching over the det | count records and grouped labels (val(coco_eval=True));
+    iou_thrs / area_rng are host fp64 arrays."""
+    _fields_ = [("det", C.c_void_p), ("det_count", C.c_void_p), ("n", C.c_int32), ("max_det", C.c_int32),
+                ("gt_box", C.c_void_p), ("gt_cls", C.c_void_p), ("gt_ofs", C.c_void_p), ("n_gt", C.c_int32),
+                ("single_cls", C.c_int32), ("nc", C.c_int32), ("iou_thrs", C.c_void_p), ("n_iou", C.c_int32),
+                ("area_rng", C.c_void_p), ("n_area", C.c_int32), ("max_dets", C.c_int32), ("dt_rank", C.c_void_p),
+                ("dt_matched", C.c_void_p), ("dt_ignored", C.c_void_p), ("gt_ignore", C.c_void_p),
+                ("invalid", C.c_void_p), ("workspace", C.c_void_p)]
+
+
 class AreaAttnDesc(C.Structure):
     _fields_ = [("qkv", View), ("y", View), ("v", View), ("heads", C.c_int32), ("area", C.c_int32),
                 ("scale", C.c_float)]
@@ -232,6 +243,8 @@ SIGNATURES = {
     "ydbl_match_predictions": ([C.POINTER(MatchDesc), _P], C.c_int),
     "ydbl_confusion_workspace": ([C.c_int32, C.c_int32, C.c_int32], C.c_int64),
     "ydbl_confusion_matrix": ([C.POINTER(ConfusionDesc), _P], C.c_int),
+    "ydbl_coco_workspace": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32], C.c_int64),
+    "ydbl_coco_match": ([C.POINTER(CocoDesc), _P], C.c_int),
     "ydbl_global_avgpool_workspace": ([C.POINTER(AvgPoolDesc)], C.c_int64),
     "ydbl_global_avgpool": ([C.POINTER(AvgPoolDesc), _P], C.c_int),
     "ydbl_bytetrack_state_bytes": ([C.c_int32, C.c_int32], C.c_int64),

@@ -644,18 +644,23 @@ class Model:
         return [Results(f, path=paths[i] if paths else f"image{i}.jpg", names=self.model.names, speed=speed,
                         boxes=lambda i=i: lazy[i]) for i, f in enumerate(frames)]
 
-    def val(self, data=None, **kwargs):
+    def val(self, data=None, *, coco_eval=False, **kwargs):
         """Detection mAP (U/engine/model.py:609-643): ``data`` = a data YAML, a dataset folder, an image folder /
         list, or in-memory batches; see ydbl.engine.validator.  rect batches by default, like the reference.
         augment=True validates the test-time-augmented predictions (U/engine/validator.py: model(img, augment=...)).
         plots (default True, as in the reference's default.yaml) accumulates ``metrics.confusion_matrix`` on the
         device; False skips it.  No image files are written either way.  verbose=True prints the per-class table.
         With save_dir, dataset-backed runs write predictions.json (save_json=True) and labels/<stem>.txt
-        (save_txt=True, save_conf for the confidence column); without save_dir nothing is written."""
+        (save_txt=True, save_conf for the confidence column); without save_dir nothing is written.
+        coco_eval=True also evaluates by the COCO protocol (per-image matching on the device, ydbl_coco_match):
+        ``metrics.coco_stats`` (mAP, AP50, AP75, APs, APm, APl, AR1, AR10, AR100, ARs, ARm, ARl),
+        ``metrics.coco_eval`` (COCOeval's precision / recall / scores arrays), ``validator.coco_summary()`` and, with
+        save_dir, coco_stats.csv.  The Ultralytics fields keep their values."""
         from .validator import DetectionValidator
 
         args = {**DEFAULTS, "conf": 0.001, "iou": 0.7, "batch": 16, "rect": True, "split": "val", "plots": True,
-                "save_json": False, "save_txt": False, "save_conf": False, "save_dir": None, **kwargs}
+                "save_json": False, "save_txt": False, "save_conf": False, "save_dir": None, **kwargs,
+                "coco_eval": bool(coco_eval)}
         check_augment(args["augment"], args["fp8"])
         self.validator = DetectionValidator(self, args)  # kept: its per-image stats (tp, conf, pred_cls, target_cls)
         return self.validator(data)

@@ -16,7 +16,15 @@ Beside the mean scalars the validator reports what the reference's does: ``metri
 the device by ydbl_confusion_matrix on the tensors the TP matrix is matched on; ``plots=False`` skips it, as in
 the reference — no image files are written either way), the per-class table (``nt_per_class``, ``nt_per_image``,
 ``seen``, ``print_results()``), and for dataset-backed runs with ``save_dir`` the ``predictions.json`` rows of
-``save_json`` and the ``labels/<stem>.txt`` files of ``save_txt`` / ``save_conf`` (no pycocotools evaluation).
+``save_json`` and the ``labels/<stem>.txt`` files of ``save_txt`` / ``save_conf``.
+
+``coco_eval=True`` adds the COCO protocol the reference reaches through pycocotools (val.py:297-337): the per-image
+matching of COCOeval.evaluateImg runs on the device (ydbl_coco_match, one launch per batch behind the two above, on
+the same tensors and label grouping), COCOeval.accumulate / summarize on the host (utils/metrics.py):
+``metrics.coco_stats`` (the 12 stats), ``metrics.coco_eval`` (precision / recall / scores in COCOeval's layout),
+``coco_summary()`` and, with ``save_dir``, ``coco_stats.csv``.  pycocotools itself is not used.  One difference
+from the reference path: that one evaluates the predictions.json rows (bbox rounded to 3 decimals, score to 5), this
+the unrounded fp32 boxes and scores.  The Ultralytics fields above are not touched by it.
 """
 
 from __future__ import annotations
@@ -31,7 +39,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..utils.metrics import IOUV, LOGGER, ConfusionMatrix, DetMetrics
+from ..utils.metrics import (COCO_AREA_RNG, COCO_IOU_THRS, COCO_MAX_DETS, IOUV, LOGGER, ConfusionMatrix, DetMetrics,
+                             coco_summary_lines)
 from .model import load_tensor_source, select_device
 
 
@@ -106,6 +115,57 @@ def match_batch(det: torch.Tensor, count: torch.Tensor, gt_box: torch.Tensor, gt
     return out.bool()
 
 
+def coco_batch(det: torch.Tensor, count: torch.Tensor, gt_box, gt_cls, batch_idx, nc: int, single_cls: bool = False,
+               grouped=None, iou_thrs=COCO_IOU_THRS, area_rng=COCO_AREA_RNG, max_dets: int = COCO_MAX_DETS[-1]) -> dict:
+    """COCO-protocol matching of one batch on the device (ydbl_coco_match): one launch for COCOeval.evaluateImg over
+    every (image, category, area range, IoU threshold).  det / count / labels as for match_batch (``grouped``: the
+    result of group_labels, to share one grouping with it).  Returns device tensors: ``rank`` int32 [B, max_det]
+    (the row's place in its image's category list by score, -1 when it takes no part), ``matched`` / ``ignored``
+    int32 [B, max_det, A] (bit t: at iou_thrs[t]), ``gt_ignore`` uint8 [N, A] (labels in grouped order) and
+    ``invalid`` int32 [B] (rows whose class is outside [0, nc)).  Nothing is read back."""
+    if det.device.type != "cuda":
+        raise RuntimeError("coco_batch runs on the GPU (ydbl_coco_match); got a CPU tensor")
+    dev = det.device
+    b, max_det = det.shape[0], det.shape[1]
+    boxes, cls, ofs, n_gt = grouped or group_labels(gt_box, gt_cls, batch_idx, b, dev)
+    det = det.float().contiguous()
+    count = count.to(dev, torch.int32).contiguous()
+    thr = np.ascontiguousarray(iou_thrs, dtype=np.float64)
+    rng = np.ascontiguousarray(area_rng, dtype=np.float64).reshape(-1, 2)
+    A = len(rng)
+    out = {"rank": torch.empty((b, max_det), dtype=torch.int32, device=dev),
+           "matched": torch.empty((b, max_det, A), dtype=torch.int32, device=dev),
+           "ignored": torch.empty((b, max_det, A), dtype=torch.int32, device=dev),
+           "gt_ignore": torch.empty((n_gt, A), dtype=torch.uint8, device=dev),
+           "invalid": torch.empty(b, dtype=torch.int32, device=dev)}
+    nws = int(_lib.lib.ydbl_coco_workspace(b, max_det, n_gt, nc))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws > 0 else None
+    d = _lib.CocoDesc(det.data_ptr(), count.data_ptr(), b, max_det, boxes.data_ptr() if n_gt else None,
+                      cls.data_ptr() if n_gt else None, ofs.data_ptr(), n_gt, int(bool(single_cls)), int(nc),
+                      thr.ctypes.data, len(thr), rng.ctypes.data, A, int(max_dets), out["rank"].data_ptr(),
+                      out["matched"].data_ptr(), out["ignored"].data_ptr(),
+                      out["gt_ignore"].data_ptr() if n_gt else None, out["invalid"].data_ptr(),
+                      ws.data_ptr() if ws is not None else None)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(_lib.lib.ydbl_coco_match(C.byref(d), stream), "ydbl_coco_match")
+    return out
+
+
+def coco_host_record(det, out, gt_cls, nc: int, single_cls: bool) -> dict:
+    """One batch's coco_batch outputs as the numpy record coco_accumulate reads: det [B, max_det, 6] and ``out`` on
+    the host, gt_cls the labels' classes in grouped order."""
+    det = det.float().numpy()
+    c = det[..., 5]
+    gc = np.asarray(gt_cls, dtype=np.float32).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        cls = np.where((c > -1) & (c < nc), c, -1).astype(np.int64)  # the kernel's rule: truncation inside (-1, nc)
+        gcls = np.where((gc > -1) & (gc < nc), gc, -1).astype(np.int64)
+    if single_cls:
+        cls, gcls = np.zeros_like(cls), np.zeros_like(gcls)
+    return {"score": det[..., 4], "cls": cls, "rank": out["rank"].numpy(), "matched": out["matched"].numpy(),
+            "ignored": out["ignored"].numpy(), "gt_cls": gcls, "gt_ignore": out["gt_ignore"].numpy().astype(bool)}
+
+
 class DetectionValidator:
     def __init__(self, model, args):
         self.model = model
@@ -123,6 +183,8 @@ class DetectionValidator:
         self.nc = len(self.model.names)
         self.confusion_matrix = ConfusionMatrix(nc=self.nc, conf=self.args["conf"])  # val.py:83
         self.jdict = []
+        self.coco_batches = []  # coco_eval=True: one host record per batch (coco_host_record)
+        self.coco_invalid = 0
         self.save_dir = Path(self.args["save_dir"]) if self.args.get("save_dir") else None
         if isinstance(data, (str, os.PathLike, dict)):
             self._run_dataset(data, dev)
@@ -137,13 +199,35 @@ class DetectionValidator:
         if len(st["tp"]) and st["tp"].any():
             self.metrics.process(st["tp"], st["conf"], st["pred_cls"], st["target_cls"])
         self.metrics.confusion_matrix = self.confusion_matrix  # finalize_metrics (val.py:174-177)
+        if self.args.get("coco_eval"):
+            self._finish_coco()
         if self.save_dir is not None and self.args.get("save_json") and self.jdict:
             self.save_dir.mkdir(parents=True, exist_ok=True)
             with open(self.save_dir / "predictions.json", "w") as f:  # U/engine/validator.py:205-208
                 json.dump(self.jdict, f)
         if self.args.get("verbose"):
             print("\n".join([self.get_desc(), *self.print_results()]))
+            if self.args.get("coco_eval"):
+                print("\n".join(self.coco_summary()))
         return self.metrics
+
+    def _finish_coco(self):
+        """COCOeval.accumulate + summarize over the batches' device matching, and coco_stats.csv under save_dir."""
+        if self.coco_invalid:
+            LOGGER.warning(f"coco_eval: {self.coco_invalid} detections had a class outside [0, {self.nc}) and were "
+                           "left out")
+        self.metrics.process_coco(self.coco_batches, self.nc)
+        if self.save_dir is not None:
+            self.save_dir.mkdir(parents=True, exist_ok=True)
+            with open(self.save_dir / "coco_stats.csv", "w") as f:
+                f.write(",".join(self.metrics.coco_stat_names) + "\n")
+                f.write(",".join(repr(float(v)) for v in self.metrics.coco_stats) + "\n")
+
+    def coco_summary(self):
+        """The twelve lines COCOeval.summarize prints, from the last val(coco_eval=True)."""
+        if self.metrics.coco_eval is None:
+            raise RuntimeError("coco_summary() needs a val(coco_eval=True) run")
+        return coco_summary_lines(self.metrics.coco_eval)
 
     def get_desc(self):
         """val.py:88-90: the table header of this fork (mAP75 is its fifth metric column)."""
@@ -232,8 +316,16 @@ class DetectionValidator:
         tp_all = match_batch(det_d, cnt_d, box_all, cls_all, bidx, self.iouv, single, grouped=grouped)
         if self.args.get("plots", True):  # val.py:144-145, :158-159
             confusion_batch(det_d, cnt_d, box_all, cls_all, bidx, self.confusion_matrix, single, grouped=grouped)
+        coco = None
+        if self.args.get("coco_eval"):
+            coco = coco_batch(det_d, cnt_d, box_all, cls_all, bidx, self.nc, single, grouped=grouped)
         tp_all = tp_all.cpu()
         det, cnt = det_d.cpu(), cnt_d.cpu().tolist()
+        if coco is not None:
+            coco = {k: v.cpu() for k, v in coco.items()}
+            self.coco_invalid += int(coco["invalid"].sum())
+            by_image = torch.argsort(torch.as_tensor(bidx).reshape(-1).long(), stable=True)  # group_labels' order
+            self.coco_batches.append(coco_host_record(det, coco, cls_all[by_image], self.nc, single))
         save = self.save_dir is not None and im_files is not None
         for si in range(b):
             self.seen += 1

@@ -5,6 +5,8 @@ Restates U/utils/metrics.py:447-452 (smooth), :505-534 (compute_ap, 101-point CO
 mAP75).  The per-image TP matrix (box_iou + match_predictions) runs on the device: ydbl_match_predictions, see
 engine/validator.py; its host restatement is the checker in oracle/metrics.py.  ConfusionMatrix (:294-445) keeps
 the reference's interface over a device accumulator that ydbl_confusion_matrix adds into.
+coco_accumulate / coco_summarize restate COCOeval.accumulate / summarize (the protocol the reference reaches through
+pycocotools, U/models/yolo/detect/val.py:297-337) over the per-image matching ydbl_coco_match does on the device.
 """
 
 from __future__ import annotations
@@ -72,6 +74,112 @@ def ap_per_class(tp, conf, pred_cls, target_cls, eps=1e-16, curves=False):
     fp = (tp / (p + eps) - tp).round()
     out = (tp, fp, p, r, f1, ap, unique_classes.astype(int))
     return out + (p_curve, r_curve, f1_curve, x, np.array(prec_values)) if curves else out
+
+
+# ---- COCO protocol (COCOeval's Params, accumulate and summarize for iouType "bbox") -------------------------------
+COCO_IOU_THRS = np.linspace(0.5, 0.95, 10)
+COCO_REC_THRS = np.linspace(0.0, 1.0, 101)
+COCO_MAX_DETS = (1, 10, 100)
+COCO_AREA_RNG = ((0.0, 1e10), (0.0, 32.0**2), (32.0**2, 96.0**2), (96.0**2, 1e10))
+COCO_AREA_LBL = ("all", "small", "medium", "large")
+COCO_STAT_NAMES = ("mAP", "AP50", "AP75", "APs", "APm", "APl", "AR1", "AR10", "AR100", "ARs", "ARm", "ARl")
+
+
+def coco_accumulate(batches, nc, iou_thrs=COCO_IOU_THRS, rec_thrs=COCO_REC_THRS, max_dets=COCO_MAX_DETS,
+                    area_rng=COCO_AREA_RNG):
+    """COCOeval.accumulate over the per-batch outputs of ydbl_coco_match (engine/validator.py coco_batch), host fp64.
+
+    batches: dicts of numpy arrays in image order — ``score`` fp32 [B, max_det], ``cls`` int [B, max_det] (the
+    category of each row), ``rank`` int32 [B, max_det] (-1: the row takes no part), ``matched`` / ``ignored`` int32
+    [B, max_det, A] (bit t: at iou_thrs[t]), ``gt_cls`` int [N] (-1: a label of no category), ``gt_ignore`` bool
+    [N, A].  Returns COCOeval's ``eval`` dict: precision [T, R, K, A, M], recall [T, K, A, M], scores like precision
+    (-1 where a category has no non-ignored label in that area range), params and counts."""
+    iou_thrs, rec_thrs = np.asarray(iou_thrs, np.float64), np.asarray(rec_thrs, np.float64)
+    T, R, K, A, M = len(iou_thrs), len(rec_thrs), int(nc), len(area_rng), len(max_dets)
+    precision, recall, scores = -np.ones((T, R, K, A, M)), -np.ones((T, K, A, M)), -np.ones((T, R, K, A, M))
+    img, cls, rank, score, dtm, dtig, gcls, gig = [], [], [], [], [], [], [], []
+    i0 = 0
+    for bt in batches:
+        keep = np.asarray(bt["rank"]) >= 0
+        bi, _ = np.nonzero(keep)
+        img.append(bi + i0)
+        i0 += keep.shape[0]
+        cls.append(np.asarray(bt["cls"])[keep])
+        rank.append(np.asarray(bt["rank"])[keep])
+        score.append(np.asarray(bt["score"])[keep].astype(np.float64))
+        dtm.append(np.asarray(bt["matched"])[keep])
+        dtig.append(np.asarray(bt["ignored"])[keep])
+        gcls.append(np.asarray(bt["gt_cls"]).reshape(-1))
+        gig.append(np.asarray(bt["gt_ignore"]).reshape(-1, A).astype(bool))
+    cat = lambda v, shape: np.concatenate(v) if v else np.zeros(shape)  # noqa: E731
+    img, cls, rank, score = cat(img, 0), cat(cls, 0), cat(rank, 0), cat(score, 0)
+    dtm, dtig, gcls, gig = cat(dtm, (0, A)), cat(dtig, (0, A)), cat(gcls, 0), cat(gig, (0, A)).astype(bool)
+    order = np.lexsort((rank, img))  # image order, each image's category list in its score order
+    img, cls, rank, score, dtm, dtig = img[order], cls[order], rank[order], score[order], dtm[order], dtig[order]
+    bits = np.arange(T)[:, None]
+    for k in range(K):
+        sk = cls == k
+        gk = gig[gcls == k]
+        for m, md in enumerate(max_dets):
+            sel = np.nonzero(sk & (rank < md))[0]
+            sel = sel[np.argsort(-score[sel], kind="mergesort")]
+            sc, nd = score[sel], len(sel)
+            for a in range(A):
+                npig = int(np.count_nonzero(~gk[:, a]))
+                if npig == 0:
+                    continue
+                mt = ((dtm[sel, a][None, :] >> bits) & 1).astype(bool)
+                ig = ((dtig[sel, a][None, :] >> bits) & 1).astype(bool)
+                tps = np.cumsum(mt & ~ig, axis=1).astype(np.float64)
+                fps = np.cumsum(~mt & ~ig, axis=1).astype(np.float64)
+                for t in range(T):
+                    tp, fp = tps[t], fps[t]
+                    rc = tp / npig
+                    pr = tp / (fp + tp + np.spacing(1))
+                    recall[t, k, a, m] = rc[-1] if nd else 0
+                    pr = np.maximum.accumulate(pr[::-1])[::-1]
+                    idx = np.searchsorted(rc, rec_thrs, side="left")
+                    ok = idx < nd
+                    q, ss = np.zeros(R), np.zeros(R)
+                    q[ok], ss[ok] = pr[idx[ok]], sc[idx[ok]]
+                    precision[t, :, k, a, m], scores[t, :, k, a, m] = q, ss
+    params = {"iouThrs": iou_thrs, "recThrs": rec_thrs, "maxDets": list(max_dets),
+              "areaRng": [list(r) for r in area_rng], "areaRngLbl": list(COCO_AREA_LBL[:A]), "catIds": list(range(K)),
+              "iouType": "bbox", "useCats": 1}
+    return {"params": params, "counts": [T, R, K, A, M], "precision": precision, "recall": recall, "scores": scores}
+
+
+def _coco_stat(ev, ap, iou_thr=None, area=0, max_det=-1):
+    """COCOeval._summarize: the mean of the entries > -1 of one slice, -1 without any."""
+    s = ev["precision"] if ap else ev["recall"]
+    if iou_thr is not None:
+        s = s[np.isclose(ev["params"]["iouThrs"], iou_thr)]
+    s = s[..., area, max_det]
+    return float(s[s > -1].mean()) if (s > -1).any() else -1.0
+
+
+_COCO_ROWS = ((1, None, 0, 2), (1, 0.5, 0, 2), (1, 0.75, 0, 2), (1, None, 1, 2), (1, None, 2, 2), (1, None, 3, 2),
+              (0, None, 0, 0), (0, None, 0, 1), (0, None, 0, 2), (0, None, 1, 2), (0, None, 2, 2), (0, None, 3, 2))
+
+
+def coco_summarize(ev):
+    """COCOeval.summarize for boxes: float64 [12] in the order of COCO_STAT_NAMES (needs the standard 4 area ranges
+    and 3 maxDets)."""
+    if ev["counts"][3] != 4 or ev["counts"][4] != 3:
+        raise ValueError("coco_summarize needs the 4 standard area ranges and 3 maxDets")
+    return np.array([_coco_stat(ev, *row) for row in _COCO_ROWS], dtype=np.float64)
+
+
+def coco_summary_lines(ev):
+    """The twelve lines COCOeval.summarize prints."""
+    p = ev["params"]
+    lines = []
+    for ap, thr, a, m in _COCO_ROWS:
+        iou = f"{p['iouThrs'][0]:0.2f}:{p['iouThrs'][-1]:0.2f}" if thr is None else f"{thr:0.2f}"
+        lines.append(" {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}".format(
+            "Average Precision" if ap else "Average Recall", "(AP)" if ap else "(AR)", iou, p["areaRngLbl"][a],
+            p["maxDets"][m], _coco_stat(ev, ap, thr, a, m)))
+    return lines
 
 
 class BoxMetric:
@@ -148,12 +256,19 @@ class DetMetrics:
 
     keys = ["metrics/precision(B)", "metrics/recall(B)", "metrics/mAP50(B)", "metrics/mAP75(B)", "metrics/mAP50-95(B)"]
     curves = ["Precision-Recall(B)", "F1-Confidence(B)", "Precision-Confidence(B)", "Recall-Confidence(B)"]
+    coco_stat_names = list(COCO_STAT_NAMES)
 
     def __init__(self, names=None):
         self.names = names or {}
         self.box = BoxMetric()
         self.speed = {}
         self.confusion_matrix = None
+        # val(coco_eval=True): COCOeval's 12 stats (float64 [12]) and its eval dict; None otherwise
+        self.coco_stats = self.coco_eval = None
+
+    def process_coco(self, batches, nc):
+        self.coco_eval = coco_accumulate(batches, nc)
+        self.coco_stats = coco_summarize(self.coco_eval)
 
     def process(self, tp, conf, pred_cls, target_cls):
         res = ap_per_class(tp, conf, pred_cls, target_cls, curves=True)
