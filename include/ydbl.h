@@ -70,6 +70,9 @@
  *                             (adaptive_avg_pool2d(x, (1, 1)).squeeze(-1).squeeze(-1) of a layer's output)
  *   ydbl_bytetrack_update  <- BYTETracker.update trackers/byte_tracker.py:293-405 as driven per image by
  *                             on_predict_postprocess_end trackers/track.py:53-87
+ *   ydbl_detect_loss       <- v8DetectionLoss.__call__ utils/loss.py:206-260 (BboxLoss :99-113, DFLoss :73-88,
+ *                             bbox_iou CIoU utils/metrics.py:74-134) + TaskAlignedAssigner utils/tal.py:40-295,
+ *                             forward only, as DetectionModel.loss nn/tasks.py:294-310 reaches it
  */
 #ifndef YDBL_H
 #define YDBL_H
@@ -717,6 +720,53 @@ typedef struct {
 } ydbl_track_desc;
 int64_t ydbl_bytetrack_state_bytes(int32_t max_tracks, int32_t max_det); /* per tracker; -1: an argument < 1 */
 int ydbl_bytetrack_update(const ydbl_track_desc* d, void* stream);
+
+/* The detection loss of a batch, forward only: v8DetectionLoss.__call__ (utils/loss.py:206-260) with bbox_decode
+ * (:197-204), BboxLoss (:99-113), DFLoss (:73-88), bbox_iou(CIoU=True) (utils/metrics.py:74-134) and the
+ * TaskAlignedAssigner (utils/tal.py:40-295; alpha 0.5, beta 6.0, eps 1e-9; make_anchors :333-345, bbox2dist :360-363),
+ * read from the Detect head's level buffers in place.  box[l] / cls[l]: the 64 box logits and the nc class logits of
+ * level l as NHWC views (channel slices of one [B,h,w,64+nc] buffer or separate; YDBL_F16 or YDBL_F32, any channel
+ * pitch, element-aligned); all arithmetic is fp32.  stride[l]: the level's stride; reg_max must be 16.
+ * gt fp32 [B][max_labels][5]: rows cls, x1, y1, x2, y2 in input pixels, zero-padded; a row whose four box values sum
+ * to <= 0 is padding (the reference's mask_gt).  A class is truncated to int and clamped into [0, nc): the caller
+ * validates it.
+ * The assignment: per label the `topk` (1..16; the reference: 10) anchors of largest align_metric =
+ * sigmoid(class logit)^0.5 * max(CIoU, 0)^6 (CIoU of the label and predicted box * stride, in pixels) among the
+ * anchors whose centre lies strictly inside the label's box (> 1e-9 on all four deltas), an equal metric going to
+ * the lower anchor index.  A ZERO METRIC IS NOT SELECTED: the reference's topk, short of positive metrics, fills up
+ * with zero-metric anchors in an order torch leaves unspecified; inside the box those become fg with target score 0
+ * and weight 0 and change none of the three sums (fg / target_gt_idx may differ from the reference only there).
+ * An anchor selected by more than one label goes to the argmax of the overlaps over ALL the image's labels (0 outside
+ * a box and for padding; first index on ties), also to one that did not select it (tal.py:284-292).  The per-label
+ * maxima of metric and overlap are taken after that, and target score = metric * max_overlap / (max_metric + 1e-9).
+ * Box and DFL terms in grid units (label / stride), DFL target clamped to [0, 14.99], BCE over every anchor and class.
+ * Outputs (each word written once; no floating-point atomics -- integer atomics for the pick counts, atomicMax on
+ * the bits of non-negative floats for the maxima -- so all of them are bit-identical from run to run):
+ *   loss fp32 [3]            box, cls, dfl: gain * sum / target_scores_sum (box and dfl 0 when nothing is fg);
+ *   target_scores_sum fp32   max(sum of target scores, 1);
+ *   per_image fp32 [B][3]    the same three sums restricted to one image, over the batch's target_scores_sum;
+ *   fg int32 [B][A], target_gt_idx int32 [B][A], target_score fp32 [B][A]: optional (NULL: not written), the
+ *                            assignment; target_score is the value that lands on the label's class.
+ * A = sum of h*w over the levels, anchors in level order, row-major.  Five launches on `stream`; no allocation, no
+ * host sync, graph-capturable, reentrant.  workspace: ydbl_detect_loss_workspace(B, A, max_labels) bytes, 16-byte
+ * aligned (-1 for an argument < 1, max_labels < 0).  YDBL_EINVAL: null descriptor / buffer, nl outside 1..3, nc < 1,
+ * reg_max != 16, topk outside 1..16, level shapes that disagree, B or max_labels > 65535, B*A*4 >= 2^31, workspace
+ * too small or misaligned. */
+typedef struct {
+  ydbl_view box[3], cls[3];
+  int32_t nl, nc, reg_max;
+  float stride[3];
+  const float* gt;
+  int32_t max_labels;
+  int32_t topk;
+  float gain_box, gain_cls, gain_dfl;   /* hyp.box / cls / dfl: 7.5 / 0.5 / 1.5 (cfg/default.yaml:99-101) */
+  float* loss; float* target_scores_sum; float* per_image;
+  int32_t* fg; int32_t* target_gt_idx; float* target_score;
+  void* workspace;
+  int64_t workspace_bytes;
+} ydbl_loss_desc;
+int64_t ydbl_detect_loss_workspace(int32_t n, int32_t anchors, int32_t max_labels);
+int ydbl_detect_loss(const ydbl_loss_desc* d, void* stream);
 
 const char* ydbl_last_error(void);
 const char* ydbl_version(void);

@@ -188,6 +188,16 @@ class TrackDesc(C.Structure):
                 ("tracked", C.c_void_p), ("out_idx", C.c_void_p), ("state", C.c_void_p), ("state_bytes", C.c_int64)]
 
 
+class LossDesc(C.Structure):
+    """ydbl_loss_desc: the detection loss (TaskAlignedAssigner + CIoU / BCE / DFL) over the Detect levels in place."""
+    _fields_ = [("box", View * 3), ("cls", View * 3), ("nl", C.c_int32), ("nc", C.c_int32), ("reg_max", C.c_int32),
+                ("stride", C.c_float * 3), ("gt", C.c_void_p), ("max_labels", C.c_int32), ("topk", C.c_int32),
+                ("gain_box", C.c_float), ("gain_cls", C.c_float), ("gain_dfl", C.c_float),
+                ("loss", C.c_void_p), ("target_scores_sum", C.c_void_p), ("per_image", C.c_void_p),
+                ("fg", C.c_void_p), ("target_gt_idx", C.c_void_p), ("target_score", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 # name -> (argtypes, restype); every entry must exist in include/ydbl.h
 _P = C.c_void_p
 _VP = C.POINTER(View)
@@ -249,6 +259,8 @@ SIGNATURES = {
     "ydbl_global_avgpool": ([C.POINTER(AvgPoolDesc), _P], C.c_int),
     "ydbl_bytetrack_state_bytes": ([C.c_int32, C.c_int32], C.c_int64),
     "ydbl_bytetrack_update": ([C.POINTER(TrackDesc), _P], C.c_int),
+    "ydbl_detect_loss_workspace": ([C.c_int32, C.c_int32, C.c_int32], C.c_int64),
+    "ydbl_detect_loss": ([C.POINTER(LossDesc), _P], C.c_int),
     "ydbl_last_error": ([], C.c_char_p),
     "ydbl_version": ([], C.c_char_p),
 }

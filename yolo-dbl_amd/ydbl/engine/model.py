@@ -64,6 +64,20 @@ def check_embed(embed, n_layers: int, augment=False, fp8=False, gather_rows=None
     return embed
 
 
+def check_loss(loss, augment=False, gather_rows=None):
+    """loss's scope guards, before any device work: the augmented forward runs three passes and has no single set of
+    levels to score (ValueError); the batch-sharded predictor's shards would each normalise by their own target
+    scores (NotImplementedError).  Returns the session's loss settings (a dict) or None."""
+    if not loss:
+        return None
+    if augment:
+        raise ValueError("loss=True with augment=True: the three augmented passes have no single set of levels to "
+                         "score; drop one of the two")
+    if gather_rows is not None:
+        raise NotImplementedError("loss=True is not implemented for the batch-sharded predictor (gather_rows)")
+    return dict(loss) if isinstance(loss, dict) else {}
+
+
 def select_device(device=None) -> torch.device:
     """U/utils/torch_utils.py select_device, GPU-only."""
     if device is None or device == "":
@@ -255,15 +269,20 @@ class Model:
 
     def session(self, batch, h, w, half=False, conf=0.25, iou=0.7, max_det=300, agnostic=False, classes=None,
                 multi_label=False, device=None, keep_pred=False, use_graph=True, fp8=False, clip=True,
-                streams=1, gather_rows=None, nms=True, fp8_calibration=None, augment=False, embed=None):
+                streams=1, gather_rows=None, nms=True, fp8_calibration=None, augment=False, embed=None, loss=None):
         """A compiled (batch, h, w, dtype, NMS settings) inference session; streams > 1 splits the batch into
         that many concurrently replayed sub-batch graphs (DetectSession); streams=None: default_streams(batch),
         the layout predict() runs and bench.py times.  augment=True: the test-time-augmentation session
         (AugmentSession: three passes, one NMS over their union; no fp8).  embed=[i, ...]: an EmbedSession -- the
         plan stops at layer max(embed) and returns the pooled layer features; the detection arguments (conf, iou, NMS
-        settings) mean nothing to it and are not part of its cache key."""
+        settings) mean nothing to it and are not part of its cache key.  loss=True (or a dict of max_labels / topk /
+        gains): ydbl_detect_loss behind the head on dense levels, one plan for the whole batch (DetectSession.loss,
+        load_labels)."""
+        loss = check_loss(loss, augment, gather_rows)
         embed = check_embed(embed, len(self.model.model), augment, fp8, gather_rows)
         augment = check_augment(augment, fp8, gather_rows)
+        if loss is not None and embed is not None:
+            raise ValueError("loss=True with embed: the truncated plan has no head to score")
         if streams is None:
             streams = default_streams(batch)
         dev = select_device(device)
@@ -285,6 +304,7 @@ class Model:
                tuple(classes) if classes is not None else None, bool(multi_label), str(dev), keep_pred, use_graph,
                float(fp8), bool(clip), int(streams), gather_rows, bool(nms),
                _calib_key(fp8_calibration), augment,
+               None if loss is None else tuple(sorted((k, str(v)) for k, v in loss.items())),
                # the remaining YDBL_* switches (plan-builder fusions in ydbl.nn.modules; YDBL_DS_LEAN / YDBL_NMS_*
                # in the C-ABI) are read at plan build or at each launch, so a captured graph keeps the routing of
                # its capture: a different switch setting is a different session
@@ -302,7 +322,7 @@ class Model:
                     s = DetectSession(self.model, batch, h, w, dtype, conf, iou, max_det, multi_label, agnostic,
                                       classes, keep_pred=keep_pred, use_graph=use_graph, device=dev, fp8=fp8,
                                       clip=clip, streams=streams, gather_rows=gather_rows, nms=nms,
-                                      fp8_calibration=fp8_calibration)
+                                      fp8_calibration=fp8_calibration, loss=loss)
             s.wsig = weights_signature(self.model)  # the weights its plans folded (see _stale)
             self._sessions[key] = s
         else:
@@ -644,7 +664,7 @@ class Model:
         return [Results(f, path=paths[i] if paths else f"image{i}.jpg", names=self.model.names, speed=speed,
                         boxes=lambda i=i: lazy[i]) for i, f in enumerate(frames)]
 
-    def val(self, data=None, *, coco_eval=False, **kwargs):
+    def val(self, data=None, *, coco_eval=False, loss=False, **kwargs):
         """Detection mAP (U/engine/model.py:609-643): ``data`` = a data YAML, a dataset folder, an image folder /
         list, or in-memory batches; see ydbl.engine.validator.  rect batches by default, like the reference.
         augment=True validates the test-time-augmented predictions (U/engine/validator.py: model(img, augment=...)).
@@ -655,13 +675,19 @@ class Model:
         coco_eval=True also evaluates by the COCO protocol (per-image matching on the device, ydbl_coco_match):
         ``metrics.coco_stats`` (mAP, AP50, AP75, APs, APm, APl, AR1, AR10, AR100, ARs, ARm, ARl),
         ``metrics.coco_eval`` (COCOeval's precision / recall / scores arrays), ``validator.coco_summary()`` and, with
-        save_dir, coco_stats.csv.  The Ultralytics fields keep their values."""
+        save_dir, coco_stats.csv.  The Ultralytics fields keep their values.
+        loss=True also scores the head's outputs against the labels (ydbl_detect_loss behind each batch's forward, on
+        the letterboxed-space labels): ``metrics.val_loss`` = (box, cls, dfl) averaged over the batches
+        (U/engine/validator.py:185, :205), ``val/box_loss`` / ``val/cls_loss`` / ``val/dfl_loss`` in
+        ``metrics.results_dict``, ``validator.image_loss`` [images, 3] in dataset order and, with save_dir,
+        val_loss.csv.  Not with augment=True (ValueError).  With the default nothing new is compiled or launched."""
         from .validator import DetectionValidator
 
         args = {**DEFAULTS, "conf": 0.001, "iou": 0.7, "batch": 16, "rect": True, "split": "val", "plots": True,
                 "save_json": False, "save_txt": False, "save_conf": False, "save_dir": None, **kwargs,
-                "coco_eval": bool(coco_eval)}
+                "coco_eval": bool(coco_eval), "loss": bool(loss)}
         check_augment(args["augment"], args["fp8"])
+        check_loss(args["loss"], args["augment"], args.get("gather_rows"))
         self.validator = DetectionValidator(self, args)  # kept: its per-image stats (tp, conf, pred_cls, target_cls)
         return self.validator(data)
 

@@ -96,7 +96,7 @@ class DetectSession:
     def __init__(self, model, batch: int, h: int, w: int, dtype=torch.float16, conf=0.25, iou=0.7, max_det=300,
                  multi_label=False, agnostic=False, classes=None, max_nms=30000, max_wh=7680, clip=True,
                  keep_pred=False, use_graph=True, device="cuda", fp8=False, streams=1, gather_rows=None, nms=True,
-                 fp8_calibration=None, _outputs=None, _bind=None):
+                 fp8_calibration=None, _outputs=None, _bind=None, loss=None):
         if fp8 and dtype != torch.float16:
             raise ValueError("fp8 operands run on the fp16 activation path (half=True)")
         if fp8 and any(type(m).__name__ == "A2C2f" for m in model.modules()):
@@ -111,6 +111,14 @@ class DetectSession:
         self.conf, self.iou, self.max_det = float(conf), float(iou), int(max_det)
         self.children = []
         self.records = None
+        # loss = {"max_labels", "topk", "gains"[, "debug"]}: ydbl_detect_loss behind the head (_emit_loss).  The loss
+        # normalises by the whole batch's target scores, so the batch stays one plan, and it reads every level's box
+        # logits, so the levels stay dense (no sparse box path)
+        self.loss = None
+        if loss is not None:
+            if gather_rows is not None:
+                raise NotImplementedError("loss is not implemented for the batch-sharded predictor (gather_rows)")
+            streams = 1
         # predict()'s in-place path (launch_bound): binding slot 0 is the session's own staging buffer (load()), slots
         # 1 and 2 alternate between predict() calls, each with its own graph (LoadTensor maximum + the plans) and its
         # own det | count outputs, kept until the slot comes round again (then copied if its Results still live)
@@ -181,7 +189,8 @@ class DetectSession:
         self.fused_candidates = self.pred is None and self._fuse_candidates(plan, cm.levels, dd)
         # The sparse box path on top of that (predict thresholds, fp16 operands only: the fp8 calibration reads
         # feats(), and below PER_IMAGE_NMS_CONF most tiles hold a candidate): _sparse_box
-        self.sparse_box = bool(self.fused_candidates and nms and not self.fp8 and self.conf >= PER_IMAGE_NMS_CONF
+        self.sparse_box = bool(loss is None and self.fused_candidates and nms and not self.fp8
+                               and self.conf >= PER_IMAGE_NMS_CONF
                                and not os.environ.get("YDBL_NO_SPARSE_BOX") and self._sparse_box(plan, cm.levels, dd))
         if not self.fused_candidates:
             plan.launch("ydbl_detect_decode", dd, what="Detect.decode", keep=[dd])
@@ -192,12 +201,36 @@ class DetectSession:
                      self.det.stride(0), self.count.stride(0), int(self.conf >= PER_IMAGE_NMS_CONF))
         if nms:  # nms=False: forward + decode only (DetectionModel.forward -> (y, feats))
             plan.launch("ydbl_nms", nd, what="NMS", keep=[nd])
+        if loss is not None:
+            self._emit_loss(plan, cm, boxes, clss, loss)
         self.plan = plan
         self.plans = [plan]
         self.use_graph = use_graph
         self._graph = None
         if hasattr(self, "bind_ptrs"):
             self._init_slots()
+
+    def _emit_loss(self, plan: Plan, cm, boxes, clss, cfg: dict):
+        """ydbl_detect_loss as the plan's last step, reading the level buffers in place: self.loss (utils.loss
+        LossBuffers) holds gt [B, max_labels, 5] -- refilled by load_labels() before a replay, like the input -- and
+        the outputs loss [3], target_scores_sum, per_image [B, 3]."""
+        from ..utils.loss import MAX_LABELS, LossBuffers, loss_gains
+
+        det = cm.detect
+        self.loss = LossBuffers(list(boxes)[:len(cm.levels)], list(clss)[:len(cm.levels)], det.stride.tolist(), det.nc,
+                                cfg.get("gains") or loss_gains(self.model), cfg.get("max_labels", MAX_LABELS),
+                                cfg.get("topk", 10), plan.device, debug=bool(cfg.get("debug")), reg_max=det.reg_max)
+        plan.buffers += self.loss.tensors()
+        plan.launch("ydbl_detect_loss", self.loss.desc, what="Detect.loss", keep=[self.loss])
+
+    def load_labels(self, gt: torch.Tensor):
+        """Refill the loss step's label buffer from a padded host / device tensor [B, max_labels, 5] (utils.loss
+        pad_targets) before the next launch."""
+        if self.loss is None:
+            raise RuntimeError("load_labels(): the session was built without loss=")
+        if tuple(gt.shape) != tuple(self.loss.gt.shape):
+            raise ValueError(f"label buffer shape {tuple(gt.shape)} != {tuple(self.loss.gt.shape)}")
+        self.loss.gt.copy_(gt, non_blocking=True)
 
     @staticmethod
     def _fuse_candidates(plan: Plan, levels, dd: DecodeDesc) -> bool:

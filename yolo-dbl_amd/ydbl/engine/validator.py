@@ -25,6 +25,16 @@ the same tensors and label grouping), COCOeval.accumulate / summarize on the hos
 ``coco_summary()`` and, with ``save_dir``, ``coco_stats.csv``.  pycocotools itself is not used.  One difference
 from the reference path: that one evaluates the predictions.json rows (bbox rounded to 3 decimals, score to 5), this
 the unrounded fp32 boxes and scores.  The Ultralytics fields above are not touched by it.
+
+``loss=True`` adds the validation loss the reference's trainer logs (U/engine/validator.py:185, :205): the session
+keeps dense Detect levels and runs ydbl_detect_loss behind each batch's forward, in the same graph, on the labels in
+letterboxed space (dataset batches: the normalised xywh they already carry; tensor batches: their xyxy pixels).  Each
+batch's numbers stay on the device until the end (one read-back); ``metrics.val_loss`` is their sum over the number of
+batches,
+``metrics.results_dict`` gains ``val/box_loss`` / ``val/cls_loss`` / ``val/dfl_loss``, ``image_loss`` is the
+[images, 3] per-image table in dataset order (each batch's rows add up to that batch's values) and, with
+``save_dir``, ``val_loss.csv`` holds both.  Without the flag none of this exists: nothing is compiled, launched,
+copied or synchronised for it.
 """
 
 from __future__ import annotations
@@ -186,6 +196,8 @@ class DetectionValidator:
         self.coco_batches = []  # coco_eval=True: one host record per batch (coco_host_record)
         self.coco_invalid = 0
         self.save_dir = Path(self.args["save_dir"]) if self.args.get("save_dir") else None
+        if self.args.get("loss"):
+            self.loss_batches = []  # per batch: device fp32 [3 + 1 + 3 * b] (loss | target_scores_sum | per_image)
         if isinstance(data, (str, os.PathLike, dict)):
             self._run_dataset(data, dev)
         else:
@@ -201,6 +213,8 @@ class DetectionValidator:
         self.metrics.confusion_matrix = self.confusion_matrix  # finalize_metrics (val.py:174-177)
         if self.args.get("coco_eval"):
             self._finish_coco()
+        if self.args.get("loss"):
+            self._finish_loss()
         if self.save_dir is not None and self.args.get("save_json") and self.jdict:
             self.save_dir.mkdir(parents=True, exist_ok=True)
             with open(self.save_dir / "predictions.json", "w") as f:  # U/engine/validator.py:205-208
@@ -222,6 +236,45 @@ class DetectionValidator:
             with open(self.save_dir / "coco_stats.csv", "w") as f:
                 f.write(",".join(self.metrics.coco_stat_names) + "\n")
                 f.write(",".join(repr(float(v)) for v in self.metrics.coco_stats) + "\n")
+
+    def _finish_loss(self):
+        """The mean over the batches (U/engine/validator.py:205: loss / len(dataloader)), the per-image table and
+        val_loss.csv under save_dir.  The one read-back of the loss path."""
+        rows = [t.cpu() for t in self.loss_batches]
+        self.batch_loss = torch.stack([r[:3] for r in rows]) if rows else torch.zeros((0, 3))
+        self.image_loss = torch.cat([r[4:].view(-1, 3) for r in rows]) if rows else torch.zeros((0, 3))
+        total = torch.zeros(3)
+        for r in rows:  # the reference's running sum, in batch order
+            total += r[:3]
+        self.metrics.val_loss = (total / max(len(rows), 1)).tolist()
+        if self.save_dir is not None:
+            self.save_dir.mkdir(parents=True, exist_ok=True)
+            files = getattr(self, "loss_files", None) or [f"image{i}" for i in range(len(self.image_loss))]
+            with open(self.save_dir / "val_loss.csv", "w") as f:
+                f.write("image,box_loss,cls_loss,dfl_loss\n")
+                f.write("all," + ",".join(repr(float(v)) for v in self.metrics.val_loss) + "\n")
+                for name, row in zip(files, self.image_loss.tolist()):
+                    f.write(f"{name}," + ",".join(repr(float(v)) for v in row) + "\n")
+
+    def _launch(self, s, im, gt):
+        """One batch through the session; with loss=True the padded labels go into the loss step's buffer first and
+        the step's outputs are copied aside on the device (no sync)."""
+        if gt is not None:
+            s.load_labels(gt)
+        out = s(im)
+        if gt is not None:
+            self.loss_batches.append(s.loss.out.clone())
+        return out
+
+    def _loss_labels(self, bidx, cls, boxes, b, scale, xywh):
+        if not self.args.get("loss"):
+            return None
+        from ..utils.loss import MAX_LABELS, pad_targets
+
+        nc = self.model.model.nc
+        if self.args.get("single_cls"):  # one class (val.py:149-150): the labels the validator scores
+            cls = torch.zeros_like(torch.as_tensor(cls).reshape(-1).float())
+        return pad_targets(bidx, cls, boxes, b, scale, self.args.get("max_labels", MAX_LABELS), xywh=xywh, nc=nc)
 
     def coco_summary(self):
         """The twelve lines COCOeval.summarize prints, from the last val(coco_eval=True)."""
@@ -254,12 +307,15 @@ class DetectionValidator:
                                   max_det=a.get("max_det", 300), multi_label=True,
                                   agnostic=a.get("agnostic_nms", False) or a.get("single_cls", False), device=dev,
                                   fp8=a.get("fp8", False), clip=clip, streams=a.get("streams") or 1,
-                                  fp8_calibration=a.get("fp8_calibration"), augment=a.get("augment", False))
+                                  fp8_calibration=a.get("fp8_calibration"), augment=a.get("augment", False),
+                                  **({"loss": {"max_labels": a["max_labels"]} if a.get("max_labels") else True}
+                                     if a.get("loss") else {}))
 
     def _run_tensor_batch(self, batch, dev):
         im = load_tensor_source(batch["img"], int(self.model.model.stride.max())).to(dev).float()
         b, _, h, w = im.shape
-        det_d, cnt_d = self._session(b, h, w, dev, clip=True)(im)
+        gt = self._loss_labels(batch["batch_idx"], batch["cls"], batch["bboxes"], b, None, xywh=False)
+        det_d, cnt_d = self._launch(self._session(b, h, w, dev, clip=True), im, gt)
         self._update(det_d, cnt_d, torch.as_tensor(batch["bboxes"]).cpu().float().reshape(-1, 4),
                      torch.as_tensor(batch["cls"]).cpu().float().reshape(-1),
                      torch.as_tensor(batch["batch_idx"]).cpu().reshape(-1))
@@ -295,7 +351,10 @@ class DetectionValidator:
             b = len(hb["frames"])
             im = letterbox_frames(hb["frames"], hb["meta"], H, W, device=dev)
             # the reference's val NMS does not clip: scale_boxes clips to the original image afterwards
-            det_d, cnt_d = self._session(b, H, W, dev, clip=False)(im)
+            gt = self._loss_labels(hb["batch_idx"], hb["cls"], hb["bboxes"], b, (W, H, W, H), xywh=True)
+            if gt is not None:
+                self.__dict__.setdefault("loss_files", []).extend(str(f) for f in hb["im_file"])
+            det_d, cnt_d = self._launch(self._session(b, H, W, dev, clip=False), im, gt)
             det_n = det_d.clone()
             gain = torch.tensor([rp[0][0] for rp in hb["ratio_pad"]], dtype=torch.float32, device=dev)
             pad = torch.tensor([rp[1] for rp in hb["ratio_pad"]], dtype=torch.float32, device=dev)

@@ -250,15 +250,15 @@ class DetectionModel(nn.Module):
 
         Runs the compiled HIP plan of x's (batch, h, w, dtype) on x's device -- forward + decode, no NMS --
         replayed as a hipGraph; fp16 input takes the half path (AutoBackend fp16, autobackend.py:145-155).
-        BN is folded and the semantics are always inference (eval) ones; training / loss (dict input) and
-        profile / visualize are not on this path.  embed=[i, ...]: _predict_once's early return (U/nn/tasks.py:158-171)
+        BN is folded and the semantics are always inference (eval) ones; profile / visualize are not on this path,
+        and neither is training: a dict input returns ``self.loss(x)``, the forward-only detection loss.  embed=[i, ...]: _predict_once's early return (U/nn/tasks.py:158-171)
         -- the tuple of B row tensors [sum C_i] in x's dtype, the named layers' pooled outputs in ascending layer
         order, from a plan that stops at max(embed) (engine.session.EmbedSession).  augment=True: _predict_augment (U/nn/tasks.py:361-398) --
         returns ``(y, None)``, y [B, 4+nc, A_tot] the three passes' de-scaled, de-flipped, tail-clipped predictions
         side by side (engine.session.AugmentSession).  Returns fresh tensors (the plan's buffers are reused by the
         next call).  CPU tensors raise: there is no CPU execution path."""
-        if isinstance(x, dict):
-            raise NotImplementedError("training loss (dict input) is outside the inference path")
+        if isinstance(x, dict):  # BaseModel.forward (U/nn/tasks.py:109-112): a batch dict asks for the loss
+            return self.loss(x, *args, **kwargs)
         if args or any(kwargs.get(k) for k in ("profile", "visualize")):
             raise NotImplementedError("profile / visualize are outside the inference path")
         augment = bool(kwargs.get("augment"))
@@ -297,13 +297,57 @@ class DetectionModel(nn.Module):
         feats = [f.contiguous() for f in s.feats()]
         return y, feats
 
-    def _forward_session(self, b, h, w, half, device, fresh=None, augment=False, embed=None):
+    MAX_LABELS = 300  # per image: the capacity of the in-graph loss's label buffer (loss(batch) with preds=None)
+
+    def init_criterion(self):
+        """U/nn/tasks.py:358-359 (DetectionModel.init_criterion)."""
+        from ..utils.loss import v8DetectionLoss
+
+        return v8DetectionLoss(self, max_labels=self.MAX_LABELS)
+
+    def loss(self, batch, preds=None):
+        """BaseModel.loss (U/nn/tasks.py:294-306): ``(loss.sum() * batch_size, loss_items)`` of a batch dict
+        ``{"img", "batch_idx", "cls", "bboxes"}`` (bboxes: normalised xywh of img), fp32 device tensors, forward only.
+        preds=None: the forward and the loss are ONE captured graph -- a session whose Detect levels stay dense with
+        ydbl_detect_loss behind the head, reading them in place; the labels go through a fixed-capacity buffer
+        (MAX_LABELS per image) refilled before the replay, like the input.  An image with more labels, or a class
+        outside [0, nc), raises ValueError on the host before anything is launched.  preds given (the ``feats`` list
+        or the ``(y, feats)`` tuple of forward): the criterion alone (utils.loss.v8DetectionLoss)."""
+        if getattr(self, "criterion", None) is None:
+            self.criterion = self.init_criterion()
+        if preds is not None:
+            return self.criterion(preds, batch)
+        x = batch["img"]
+        if not isinstance(x, torch.Tensor) or x.ndim != 4:
+            raise TypeError("DetectionModel.loss takes batch['img'] as a BCHW tensor")
+        b, _, h, w = x.shape
+        gt = self.criterion.preprocess(batch, b, (h, w))  # host guards: before any device work
+        if x.device.type != "cuda":
+            raise RuntimeError(f"ydbl runs on MI355X (gfx950) only: input on {x.device}, move it to a cuda device")
+        if x.dtype not in (torch.float32, torch.float16):
+            raise TypeError(f"input dtype {x.dtype}: float32 or float16 (half) expected")
+        if x.shape[1] != self.yaml["ch"]:
+            raise ValueError(f"input has {x.shape[1]} channels, the model {self.yaml['ch']}")
+        half = x.dtype == torch.float16
+        s = self._forward_session(b, h, w, half, x.device, loss=True)
+        s.load_labels(gt)
+        s(x.float())
+        sig = weights_signature(self)
+        if sig != s.wsig:  # weights edited since the plan was compiled: rebuild, run again
+            s = self._forward_session(b, h, w, half, x.device, fresh=sig, loss=True)
+            s.load_labels(gt)
+            s(x.float())
+        items = s.loss.loss.clone()
+        return items.sum() * b, items
+
+    def _forward_session(self, b, h, w, half, device, fresh=None, augment=False, embed=None, loss=False):
         from ..engine.session import AugmentSession, DetectSession, EmbedSession, default_streams
 
         cache = self.__dict__.setdefault("_fwd_sessions", {})
         # compiled plans hold the routing of the YDBL_* switches at build time (part of the key) and BN-folded
         # copies of the weights (the session's wsig, checked by forward() after each launch)
-        key = (b, h, w, half, str(device), ydbl_env(), augment) + ((embed,) if embed else ())
+        key = ((b, h, w, half, str(device), ydbl_env(), augment) + ((embed,) if embed else ())
+               + ((("loss", self.MAX_LABELS),) if loss else ()))
         s = cache.pop(key, None)
         if s is not None and fresh is not None and s.wsig != fresh:
             s = None  # weights changed since this plan was built
@@ -314,6 +358,9 @@ class DetectionModel(nn.Module):
                 if embed:
                     s = EmbedSession(self, b, h, w, torch.float16 if half else torch.float32, embed, device=device,
                                      streams=default_streams(b))
+                elif loss:  # forward + decode + ydbl_detect_loss on dense levels, one plan (the batch's normaliser)
+                    s = DetectSession(self, b, h, w, torch.float16 if half else torch.float32, keep_pred=True,
+                                      nms=False, device=device, streams=1, loss={"max_labels": self.MAX_LABELS})
                 else:
                     s = (AugmentSession if augment else DetectSession)(
                         self, b, h, w, torch.float16 if half else torch.float32, keep_pred=True, nms=False,

@@ -257,6 +257,7 @@ class DetMetrics:
     keys = ["metrics/precision(B)", "metrics/recall(B)", "metrics/mAP50(B)", "metrics/mAP75(B)", "metrics/mAP50-95(B)"]
     curves = ["Precision-Recall(B)", "F1-Confidence(B)", "Precision-Confidence(B)", "Recall-Confidence(B)"]
     coco_stat_names = list(COCO_STAT_NAMES)
+    loss_keys = ["val/box_loss", "val/cls_loss", "val/dfl_loss"]  # label_loss_items(prefix="val")
 
     def __init__(self, names=None):
         self.names = names or {}
@@ -296,7 +297,11 @@ class DetMetrics:
     @property
     def results_dict(self):
         b = self.box
-        return dict(zip(self.keys + ["fitness"], [b.mp, b.mr, b.map50, b.map75, b.map, 0.1 * b.map50 + 0.9 * b.map]))
+        d = dict(zip(self.keys + ["fitness"], [b.mp, b.mr, b.map50, b.map75, b.map, 0.1 * b.map50 + 0.9 * b.map]))
+        val_loss = self.__dict__.get("val_loss")  # set by val(loss=True) only (U/engine/validator.py:205)
+        if val_loss is not None:
+            d.update(zip(self.loss_keys, val_loss))
+        return d
 
 
 class ConfusionMatrix:
