@@ -73,6 +73,9 @@
  *   ydbl_detect_loss       <- v8DetectionLoss.__call__ utils/loss.py:206-260 (BboxLoss :99-113, DFLoss :73-88,
  *                             bbox_iou CIoU utils/metrics.py:74-134) + TaskAlignedAssigner utils/tal.py:40-295,
  *                             forward only, as DetectionModel.loss nn/tasks.py:294-310 reaches it
+ *   ydbl_detect_loss_grad  <- autograd's backward of the same call: BCE utils/loss.py:247, BboxLoss :99-113 with
+ *                             bbox_decode :197-204, DFLoss :73-88, bbox_iou CIoU utils/metrics.py:102-130 (alpha
+ *                             under no_grad :128-129); the assigner is a constant (utils/loss.py:233-243)
  */
 #ifndef YDBL_H
 #define YDBL_H
@@ -767,6 +770,48 @@ typedef struct {
 } ydbl_loss_desc;
 int64_t ydbl_detect_loss_workspace(int32_t n, int32_t anchors, int32_t max_labels);
 int ydbl_detect_loss(const ydbl_loss_desc* d, void* stream);
+
+/* The gradient of the detection loss: d(loss.sum() * batch_size) / d(level logits) as the reference's autograd
+ * defines it for v8DetectionLoss.__call__ (utils/loss.py:206-260), given the assignment ydbl_detect_loss wrote.  The
+ * assigner's outputs are constants there -- it runs under torch.no_grad() on detached inputs (:233-243) -- so fg,
+ * target_gt_idx, target_score and target_scores_sum are inputs here and receive no gradient, nor do the labels.
+ * box / cls / nl / nc / reg_max / stride / gt / max_labels / gains: as in ydbl_loss_desc, the same buffers.
+ * With S = target_scores_sum, K = (grad_scale ? *grad_scale : 1) * batch_scale (batch_scale: the reference's
+ * `* batch_size`, :260; grad_scale: a device fp32 scalar, the upstream gradient of the total), and for a foreground
+ * anchor w = target_score and the label gt[b][target_gt_idx]:
+ *   class logits, every anchor and class (BCEWithLogitsLoss, :247): K * gain_cls / S * (sigmoid(x) - t), t = w on
+ *     the label's class of a foreground anchor, 0 elsewhere;
+ *   box logits of an anchor that is not foreground: 0 (written; the logits are not read);
+ *   box logits of a foreground anchor, per side s of l, t, r, b with p = softmax over the side's 16 bins and
+ *     d_s = sum j * p_j (bbox_decode, :197-204):
+ *       K * gain_box / S * w * (-dCIoU/dd_s) * p_j * (j - d_s)                      (BboxLoss, :99-106)
+ *     + K * gain_dfl / S * w / 4 * (p_j - wl * [j == tl] - wr * [j == tl + 1])        (DFLoss, :73-88, :107-109)
+ *     The CIoU is bbox_iou(xywh=False, CIoU=True) (utils/metrics.py:102-130) of the predicted box (ax - d_l, ay - d_t,
+ *     ax + d_r, ay + d_b) and label / stride, eps = 1e-7 on h1, h2, union and c2; ALPHA IS A CONSTANT (computed
+ *     under torch.no_grad(), :128-129); the gradient passes through v and through the min / max / clamp(0)
+ *     selections (a tie takes one side).  The DFL target is bbox2dist clamped to [0, 14.99], tl its integer part.
+ * gbox[l] / gcls[l]: output views of the shapes of box[l] / cls[l], YDBL_F16 or YDBL_F32 independently of the inputs,
+ * any channel pitch; lanes between c and the pitch are not touched.  All arithmetic is fp32, K included, and a value
+ * is rounded once, to the output view's dtype (a loss scale in grad_scale therefore keeps the small fp16 gradients).
+ * Every output word is written exactly once, no atomics: bit-identical from run to run and across pitches.  A whole
+ * group of 8 channels moves as 16-byte accesses at element alignment (any pitch), the nc % 8 tail element by element.
+ * One launch on `stream`; no allocation, no workspace, no host sync, graph-capturable, reentrant.  YDBL_EINVAL: as
+ * ydbl_detect_loss for the shared fields, a null assignment buffer, a null gradient view or one whose shape differs
+ * from its input's, B * A >= 2^31. */
+typedef struct {
+  ydbl_view box[3], cls[3];
+  int32_t nl, nc, reg_max;
+  float stride[3];
+  const float* gt;
+  int32_t max_labels;
+  float gain_box, gain_cls, gain_dfl;
+  const int32_t* fg; const int32_t* target_gt_idx; const float* target_score;
+  const float* target_scores_sum;
+  const float* grad_scale;
+  float batch_scale;
+  ydbl_view gbox[3], gcls[3];
+} ydbl_loss_grad_desc;
+int ydbl_detect_loss_grad(const ydbl_loss_grad_desc* d, void* stream);
 
 const char* ydbl_last_error(void);
 const char* ydbl_version(void);

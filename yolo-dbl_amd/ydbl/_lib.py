@@ -198,6 +198,16 @@ class LossDesc(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class LossGradDesc(C.Structure):
+    """ydbl_loss_grad_desc: d(loss.sum() * batch_size) / d(level logits) given the assignment ydbl_detect_loss wrote."""
+    _fields_ = [("box", View * 3), ("cls", View * 3), ("nl", C.c_int32), ("nc", C.c_int32), ("reg_max", C.c_int32),
+                ("stride", C.c_float * 3), ("gt", C.c_void_p), ("max_labels", C.c_int32),
+                ("gain_box", C.c_float), ("gain_cls", C.c_float), ("gain_dfl", C.c_float),
+                ("fg", C.c_void_p), ("target_gt_idx", C.c_void_p), ("target_score", C.c_void_p),
+                ("target_scores_sum", C.c_void_p), ("grad_scale", C.c_void_p), ("batch_scale", C.c_float),
+                ("gbox", View * 3), ("gcls", View * 3)]
+
+
 # name -> (argtypes, restype); every entry must exist in include/ydbl.h
 _P = C.c_void_p
 _VP = C.POINTER(View)
@@ -261,6 +271,7 @@ SIGNATURES = {
     "ydbl_bytetrack_update": ([C.POINTER(TrackDesc), _P], C.c_int),
     "ydbl_detect_loss_workspace": ([C.c_int32, C.c_int32, C.c_int32], C.c_int64),
     "ydbl_detect_loss": ([C.POINTER(LossDesc), _P], C.c_int),
+    "ydbl_detect_loss_grad": ([C.POINTER(LossGradDesc), _P], C.c_int),
     "ydbl_last_error": ([], C.c_char_p),
     "ydbl_version": ([], C.c_char_p),
 }

@@ -1,8 +1,11 @@
 """The detection loss on the device: ``v8DetectionLoss`` (U/utils/loss.py:157-260) over ydbl_detect_loss.
 
-Forward only -- the TaskAlignedAssigner (U/utils/tal.py:40-295) and the CIoU / BCE / DFL terms in one C-ABI call
-(csrc/loss.hip) that reads the Detect head's level maps in place.  There is no backward pass and no training here
-(DESIGN.md §8); the numbers are the reference's ``val/box_loss``, ``val/cls_loss`` and ``val/dfl_loss``.
+The TaskAlignedAssigner (U/utils/tal.py:40-295) and the CIoU / BCE / DFL terms in one C-ABI call (csrc/loss.hip)
+that reads the Detect head's level maps in place; the numbers are the reference's ``val/box_loss``,
+``val/cls_loss`` and ``val/dfl_loss``.  The criterion is differentiable: when a level map requires grad the call
+goes through a ``torch.autograd.Function`` whose backward is one ydbl_detect_loss_grad launch (csrc/loss_grad.hip)
+over the assignment the forward kept, so it can stand in for ``model.criterion`` in a PyTorch trainer.  The network
+itself has no backward pass here.
 
 Host-side pieces (pure torch on the CPU, usable without a GPU): ``loss_gains`` (hyp.box / cls / dfl),
 ``check_labels`` (the guards: capacity and class range, raised before anything is launched) and ``pad_targets``
@@ -167,7 +170,9 @@ class v8DetectionLoss:
     batch_size, loss_items)`` as fp32 device tensors, without a host sync.  ``preds``: the ``feats`` list or the
     ``(y, feats)`` tuple of DetectionModel.forward; ``batch``: ``batch_idx [N]``, ``cls [N]`` or ``[N, 1]``,
     ``bboxes [N, 4]`` normalised xywh of the input.  After a call ``target_scores_sum`` and ``per_image`` hold the
-    batch's normaliser and the [B, 3] per-image table (rows add up to loss_items)."""
+    batch's normaliser and the [B, 3] per-image table (rows add up to loss_items).  With grad mode on and a level map
+    that requires grad, the total carries a ``grad_fn`` (once differentiable; ``loss_items`` stays detached) and
+    ``backward()`` delivers d(total)/d(level map) to every map; otherwise the call is the plain forward."""
 
     def __init__(self, model, tal_topk: int = 10, max_labels: int = MAX_LABELS):
         m = model.model[-1]  # Detect() module
@@ -196,6 +201,9 @@ class v8DetectionLoss:
             raise ValueError("preds holds no level maps (an augmented forward returns (y, None))")
         b, _, h0, w0 = feats[0].shape
         gt = self.preprocess(batch, b, (h0 * self.stride[0], w0 * self.stride[0]))  # host guards first
+        if torch.is_grad_enabled() and any(isinstance(f, torch.Tensor) and f.requires_grad for f in feats):
+            total, items = _DetectionLossFn.apply(self, gt, *feats)
+            return total, items
         boxes, clss, keep = level_views(feats)
         dev = keep[0].device
         with torch.cuda.device(dev):
@@ -204,3 +212,89 @@ class v8DetectionLoss:
             bufs.launch()  # (same stream as the allocations: the caching allocator keeps the order)
         self.target_scores_sum, self.per_image = bufs.target_scores_sum, bufs.per_image
         return bufs.loss.sum() * b, bufs.loss
+
+
+# pitch of the gradient buffers in elements, rounded up to this: dense (the kernel's 16-byte stores need element
+# alignment only)
+GRAD_PITCH_ALIGN = 1
+
+
+class LossGradBuffers:
+    """The device side of one ydbl_detect_loss_grad call: per level one channels-last gradient buffer [B, H, W, pitch]
+    in the level's dtype (pitch: 64 + nc rounded up to ``pitch_align`` elements; dense by default) and the descriptor
+    over
+    the channels-last level tensors ``keep`` (level_views), the label buffer ``gt`` and the assignment the forward
+    wrote.  ``grad_scale``: a device fp32 scalar (the upstream gradient of the total) or None for 1."""
+
+    def __init__(self, keep, strides, nc: int, gains, gt, fg, target_gt_idx, target_score, target_scores_sum,
+                 batch_scale: float, grad_scale=None, pitch_align: int = GRAD_PITCH_ALIGN):
+        d = _lib.LossGradDesc()
+        d.nl, d.nc, d.reg_max, d.max_labels = len(keep), int(nc), 16, int(gt.shape[1])
+        d.gain_box, d.gain_cls, d.gain_dfl = (float(g) for g in gains)
+        d.gt, d.fg, d.target_gt_idx = gt.data_ptr(), fg.data_ptr(), target_gt_idx.data_ptr()
+        d.target_score, d.target_scores_sum = target_score.data_ptr(), target_scores_sum.data_ptr()
+        d.batch_scale = float(batch_scale)
+        if grad_scale is not None:
+            d.grad_scale = grad_scale.data_ptr()
+        self.grads = []
+        for i, f in enumerate(keep):
+            b, c, h, w = f.shape
+            pitch = -(-c // pitch_align) * pitch_align
+            g = torch.empty((b, h, w, pitch), dtype=f.dtype, device=f.device)
+            self.grads.append(g)
+            dt, es, sw = _lib.dtype_code(f.dtype), f.element_size(), f.stride(3)
+            d.box[i] = _lib.View(f.data_ptr(), b, h, w, 64, sw, dt)
+            d.cls[i] = _lib.View(f.data_ptr() + 64 * es, b, h, w, c - 64, sw, dt)
+            d.gbox[i] = _lib.View(g.data_ptr(), b, h, w, 64, pitch, dt)
+            d.gcls[i] = _lib.View(g.data_ptr() + 64 * es, b, h, w, c - 64, pitch, dt)
+            d.stride[i] = float(strides[i])
+        self.channels = [f.shape[1] for f in keep]
+        self.desc, self.keep = d, (keep, gt, fg, target_gt_idx, target_score, target_scores_sum, grad_scale)
+
+    def launch(self, stream=None):
+        dev = self.grads[0].device
+        s = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream if stream is None else stream)
+        _lib.check(_lib.lib.ydbl_detect_loss_grad(C.byref(self.desc), s), "ydbl_detect_loss_grad")
+
+    def views(self):
+        """The gradients as [B, 64+nc, H, W] views of the channels-last buffers."""
+        return [g[..., :c].permute(0, 3, 1, 2) for g, c in zip(self.grads, self.channels)]
+
+
+class _DetectionLossFn(torch.autograd.Function):
+    """``criterion(feats, batch)`` with a backward: the forward is the same ydbl_detect_loss call with the assignment
+    kept, the backward one ydbl_detect_loss_grad launch.  The assignment, the labels and target_scores_sum are
+    constants, as in the reference (U/utils/loss.py:233-243); ``loss_items`` carries no gradient (``loss.detach()``,
+    :260)."""
+
+    @staticmethod
+    def forward(ctx, crit, gt, *feats):
+        boxes, clss, keep = level_views(feats)
+        dev = keep[0].device
+        b = boxes[0].n
+        with torch.cuda.device(dev):
+            bufs = LossBuffers(boxes, clss, crit.stride, crit.nc, crit.gains, crit.max_labels, crit.tal_topk, dev,
+                               debug=True)
+            bufs.gt.copy_(gt, non_blocking=True)
+            bufs.launch()
+            total = bufs.loss.sum() * b
+        crit.target_scores_sum, crit.per_image = bufs.target_scores_sum, bufs.per_image
+        ctx.save_for_backward(*keep, bufs.gt, bufs.fg, bufs.target_gt_idx, bufs.target_score, bufs.target_scores_sum)
+        ctx.crit, ctx.nl, ctx.batch = crit, len(keep), b
+        ctx.in_dtypes = [f.dtype for f in feats]
+        ctx.mark_non_differentiable(bufs.loss)
+        return total, bufs.loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_total, _g_items):
+        crit, nl = ctx.crit, ctx.nl
+        saved = ctx.saved_tensors
+        keep, assignment = saved[:nl], saved[nl:]
+        dev = keep[0].device
+        with torch.cuda.device(dev):
+            scale = g_total.detach().to(device=dev, dtype=torch.float32).reshape(1).contiguous()
+            gb = LossGradBuffers(keep, crit.stride, crit.nc, crit.gains, *assignment, float(ctx.batch), scale)
+            gb.launch()  # (same stream as the allocations: the caching allocator keeps the order)
+        grads = [g if g.dtype == dt else g.to(dt) for g, dt in zip(gb.views(), ctx.in_dtypes)]
+        return (None, None, *grads)
