@@ -12,8 +12,10 @@ execution path (``device='cpu'`` raises).
 
 from __future__ import annotations
 
+import operator
 import time
 from collections import OrderedDict
+from dataclasses import fields
 from pathlib import Path
 
 import numpy as np
@@ -21,7 +23,7 @@ import torch
 
 from ..nn.tasks import DetectionModel, normalize_embed, weights_signature, ydbl_env
 from .results import Results
-from .session import AugmentSession, DetectSession, EmbedSession, default_streams
+from .session import AugmentSession, DetectOptions, DetectSession, EmbedSession, default_streams
 
 DEFAULTS = {"conf": 0.25, "iou": 0.7, "max_det": 300, "half": False, "fp8": False, "device": None, "agnostic_nms": False,
             "classes": None, "batch": 1, "verbose": False, "imgsz": 640,
@@ -143,6 +145,23 @@ def _calib_key(cal):
     return fp
 
 
+_OPTION_NAMES = tuple(f.name for f in fields(DetectOptions))
+_OPTION_VALUES = operator.attrgetter(*_OPTION_NAMES)
+_I_CALIB, _I_LOSS = _OPTION_NAMES.index("fp8_calibration"), _OPTION_NAMES.index("loss")
+
+
+def session_key(opt: DetectOptions, batch, h, w, dev, streams, gather_rows=None, augment=False) -> tuple:
+    """Session-cache key of a detection session: the shape, EVERY field of its options record (the calibration by
+    _calib_key, the loss settings by their sorted items), the placement and the YDBL_* switches -- those (plan-builder
+    fusions in ydbl.nn.modules; YDBL_DS_LEAN / YDBL_NMS_* in the C-ABI) are read at plan build or at each launch, so
+    a captured graph keeps the routing of its capture: a different switch setting is a different session."""
+    o = list(_OPTION_VALUES(opt))
+    o[_I_CALIB] = _calib_key(o[_I_CALIB])
+    if o[_I_LOSS] is not None:
+        o[_I_LOSS] = tuple(sorted((k, str(v)) for k, v in o[_I_LOSS].items()))
+    return (batch, h, w, *o, str(dev), int(streams), gather_rows, augment, ydbl_env())
+
+
 def _scale_consts(dev):
     """(1.0, fp32(1/255)) as 0-dim fp32 tensors on `dev` (made once)."""
     c = _SCALES.get(dev)
@@ -150,6 +169,13 @@ def _scale_consts(dev):
         c = _SCALES[dev] = (torch.ones((), dtype=torch.float32, device=dev),
                             torch.full((), 1.0 / 255.0, dtype=torch.float32, device=dev))
     return c
+
+
+def _load_tensor_scale(im: torch.Tensor) -> torch.Tensor:
+    """LoadTensor's /255 rule for a device batch, without a host sync: fp32(1/255) when its maximum is > 1, else 1."""
+    one, inv = _scale_consts(im.device)
+    thr = 1.0 + (torch.finfo(im.dtype).eps if im.is_floating_point() else 0.0)
+    return torch.where(im.amax() > thr, inv, one)
 
 
 class _LazyHWC:
@@ -289,41 +315,25 @@ class Model:
         dtype = torch.float16 if (half or fp8) else torch.float32
         if embed is not None:
             key = ("embed", embed, batch, h, w, dtype, str(dev), use_graph, int(streams), ydbl_env())
-            s = self._sessions.get(key)
-            if s is None:
-                while len(self._sessions) >= self.MAX_SESSIONS:
-                    self._sessions.popitem(last=False)
-                with torch.cuda.device(dev):
-                    s = EmbedSession(self.model, batch, h, w, dtype, embed, dev, int(streams), use_graph=use_graph)
-                s.wsig = weights_signature(self.model)
-                self._sessions[key] = s
-            else:
-                self._sessions.move_to_end(key)
-            return s
-        key = (batch, h, w, dtype, float(conf), float(iou), int(max_det), bool(agnostic),
-               tuple(classes) if classes is not None else None, bool(multi_label), str(dev), keep_pred, use_graph,
-               float(fp8), bool(clip), int(streams), gather_rows, bool(nms),
-               _calib_key(fp8_calibration), augment,
-               None if loss is None else tuple(sorted((k, str(v)) for k, v in loss.items())),
-               # the remaining YDBL_* switches (plan-builder fusions in ydbl.nn.modules; YDBL_DS_LEAN / YDBL_NMS_*
-               # in the C-ABI) are read at plan build or at each launch, so a captured graph keeps the routing of
-               # its capture: a different switch setting is a different session
-               ydbl_env())
+            return self._cached_session(key, dev, lambda: EmbedSession(self.model, batch, h, w, dtype, embed, dev,
+                                                                       int(streams), use_graph=use_graph))
+        opt = DetectOptions(dtype, conf, iou, max_det, multi_label, agnostic, classes, clip=clip, keep_pred=keep_pred,
+                            use_graph=use_graph, nms=nms, fp8=fp8, fp8_calibration=fp8_calibration, loss=loss)
+        cls, rows = (AugmentSession, {}) if augment else (DetectSession, {"gather_rows": gather_rows})
+        return self._cached_session(session_key(opt, batch, h, w, dev, streams, gather_rows, augment), dev,
+                                    lambda: cls(self.model, batch, h, w, device=dev, streams=streams, options=opt, **rows))
+
+    def _cached_session(self, key, dev, build):
+        """The session cached under `key` (now the most recently used), else build()'s, made on `dev` in place of the
+        least recently used one (its buffers go with the last reference) and stamped with the weights its plans
+        folded (wsig, see _stale)."""
         s = self._sessions.get(key)
         if s is None:
             while len(self._sessions) >= self.MAX_SESSIONS:
-                self._sessions.popitem(last=False)  # least recently used; its buffers go with the last reference
+                self._sessions.popitem(last=False)
             with torch.cuda.device(dev):
-                if augment:
-                    s = AugmentSession(self.model, batch, h, w, dtype, conf, iou, max_det, multi_label, agnostic,
-                                       classes, keep_pred=keep_pred, use_graph=use_graph, device=dev, clip=clip,
-                                       streams=streams, nms=nms)
-                else:
-                    s = DetectSession(self.model, batch, h, w, dtype, conf, iou, max_det, multi_label, agnostic,
-                                      classes, keep_pred=keep_pred, use_graph=use_graph, device=dev, fp8=fp8,
-                                      clip=clip, streams=streams, gather_rows=gather_rows, nms=nms,
-                                      fp8_calibration=fp8_calibration, loss=loss)
-            s.wsig = weights_signature(self.model)  # the weights its plans folded (see _stale)
+                s = build()
+            s.wsig = weights_signature(self.model)
             self._sessions[key] = s
         else:
             self._sessions.move_to_end(key)
@@ -344,6 +354,23 @@ class Model:
         for k in [k for k, v in self._sessions.items() if v is s]:
             del self._sessions[k]
         return True
+
+    @staticmethod
+    def _session_kw(args, dev, clip=True) -> dict:
+        """session()'s keywords of a predict() / track() call's merged arguments; clip=False for letterboxed frames
+        (the reference's NMS does not clip: boxes are clipped to the frame by scale_boxes)."""
+        return dict(half=args["half"], conf=args["conf"], iou=args["iou"], max_det=args["max_det"],
+                    agnostic=args["agnostic_nms"], classes=args["classes"], device=dev, fp8=args["fp8"], clip=clip,
+                    streams=args["streams"], fp8_calibration=args["fp8_calibration"], augment=args["augment"])
+
+    def _launch(self, s, shape, kw, run):
+        """run(s), a launch on session `s` = self.session(*shape, **kw); when the weights were edited since `s` was
+        compiled (_stale) the session is rebuilt and launched again (run(s, True)).  Returns (session, run's result)."""
+        out = run(s, False)
+        if self._stale(s):
+            s = self.session(*shape, **kw)
+            out = run(s, True)
+        return s, out
 
     def predict(self, source=None, stream=False, **kwargs):
         """U/engine/model.py:501-560 + DetectionPredictor.postprocess (U/models/yolo/detect/predict.py:23-41).
@@ -383,28 +410,22 @@ class Model:
         if im.device != dev:  # host tensors are scaled on the host, where the reference's LoadTensor does it, then moved
             im = load_tensor_source(im).to(dev, non_blocking=True).float()
         b, _, h, w = im.shape
-        kw = dict(half=args["half"], conf=args["conf"], iou=args["iou"], max_det=args["max_det"],
-                  agnostic=args["agnostic_nms"], classes=args["classes"], device=dev, fp8=args["fp8"],
-                  streams=args["streams"], fp8_calibration=args["fp8_calibration"], augment=args["augment"])
+        kw = self._session_kw(args, dev)
         s = self.session(b, h, w, **kw)
         t1 = time.perf_counter()
-        one, inv = _scale_consts(dev)
-        thr = 1.0 + (torch.finfo(im.dtype).eps if im.is_floating_point() else 0.0)
-        bo = None
-        if s.can_bind(im):
-            # read in place: the plans' input binding points at im, and the stem kernels apply LoadTensor's /255
-            # rule from its device-side maximum (no staging copy, no host sync, no per-call copy of the outputs;
-            # DetectSession.launch_bound)
-            bo = s.launch_bound(im)
-        else:
+
+        def run(s, again):
+            if not again and s.can_bind(im):
+                # read in place: the plans' input binding points at im, and the stem kernels apply LoadTensor's /255
+                # rule from its device-side maximum (no staging copy, no host sync, no per-call copy of the outputs;
+                # DetectSession.launch_bound)
+                return s.launch_bound(im), None, None, None
             # LoadTensor's /255 rule on the device without a host sync: the input copy multiplies by fp32(1/255)
             # when max > 1 (torch's GPU x / 255.0 is exactly that product), by 1 otherwise
-            scale = torch.where(im.amax() > thr, inv, one)
-            det, cnt = s(im, scale)
-        if self._stale(s):  # weights edited since the session was compiled: rebuild and run again
-            s = self.session(b, h, w, **kw)
-            scale = torch.where(im.amax() > thr, inv, one)
-            (det, cnt), bo = s(im, scale), None
+            scale = _load_tensor_scale(im)
+            return (None, *s(im, scale), scale)
+
+        s, (bo, det, cnt, scale) = self._launch(s, (b, h, w), kw, run)
         # no host sync here: each image's boxes are a view of the batch's det, cut at its count when first accessed
         # (_LazyCounts: one sync for the batch) -- on the copy path one device copy of det | count made now (the
         # session's buffers are reused by the next call); orig_img a view of the input batch (HWC, as LoadTensor
@@ -459,15 +480,8 @@ class Model:
     def _embed_batch(self, im, args, dev, load_tensor=False):
         b, _, h, w = im.shape
         kw = dict(half=args["half"], device=dev, streams=args["streams"], embed=args["embed"])
-        scale = None
-        if load_tensor:  # LoadTensor's /255 rule on the device, without a host sync (as predict()'s copy path)
-            one, inv = _scale_consts(dev)
-            thr = 1.0 + (torch.finfo(im.dtype).eps if im.is_floating_point() else 0.0)
-            scale = torch.where(im.amax() > thr, inv, one)
-        s = self.session(b, h, w, **kw)
-        out = s(im, scale)
-        if self._stale(s):  # weights edited since the session was compiled: rebuild and run again
-            out = self.session(b, h, w, **kw)(im, scale)
+        scale = _load_tensor_scale(im) if load_tensor else None  # (as predict()'s copy path)
+        _, out = self._launch(self.session(b, h, w, **kw), (b, h, w), kw, lambda s, _: s(im, scale))
         return out.clone().unbind(0)
 
     def embed(self, source=None, stream=False, **kwargs):
@@ -487,18 +501,10 @@ class Model:
         stride = int(self.model.stride.max())
         im = letterbox_batch(frames, imgsz, stride=stride, device=dev)
         b, _, h, w = im.shape
-        # the reference's NMS does not clip: boxes are clipped to the frame by scale_boxes
-        s = self.session(b, h, w, half=args["half"], conf=args["conf"], iou=args["iou"], max_det=args["max_det"],
-                         agnostic=args["agnostic_nms"], classes=args["classes"], device=dev, fp8=args["fp8"],
-                         clip=False, streams=args["streams"], fp8_calibration=args["fp8_calibration"],
-                         augment=args["augment"])
+        kw = self._session_kw(args, dev, clip=False)
+        s = self.session(b, h, w, **kw)
         t1 = time.perf_counter()
-        det, cnt = s(im)
-        if self._stale(s):
-            det, cnt = self.session(b, h, w, half=args["half"], conf=args["conf"], iou=args["iou"],
-                                    max_det=args["max_det"], agnostic=args["agnostic_nms"], classes=args["classes"],
-                                    device=dev, fp8=args["fp8"], clip=False, streams=args["streams"],
-                                    fp8_calibration=args["fp8_calibration"], augment=args["augment"])(im)
+        _, (det, cnt) = self._launch(s, (b, h, w), kw, lambda s, _: s(im))
         counts = cnt.tolist()
         t2 = time.perf_counter()
         results = []
@@ -606,19 +612,13 @@ class Model:
         if im.device != dev:
             im = load_tensor_source(im).to(dev, non_blocking=True).float()
         b, _, h, w = im.shape
-        kw = dict(half=args["half"], conf=args["conf"], iou=args["iou"], max_det=args["max_det"],
-                  agnostic=args["agnostic_nms"], classes=args["classes"], device=dev, fp8=args["fp8"],
-                  streams=args["streams"], fp8_calibration=args["fp8_calibration"], augment=args["augment"])
+        kw = self._session_kw(args, dev)
         ts = self._tracker_state(dev, cfg, args["max_det"], track_rows, b, persist, max_tracks)
         s = self.session(b, h, w, **kw)
         t1 = time.perf_counter()
-        one, inv = _scale_consts(dev)
-        thr = 1.0 + (torch.finfo(im.dtype).eps if im.is_floating_point() else 0.0)
-        scale = torch.where(im.amax() > thr, inv, one)
-        det, cnt = s(im, scale)  # the session's copy path; the in-place binding is not needed here
-        if self._stale(s):
-            s = self.session(b, h, w, **kw)
-            det, cnt = s(im, scale)
+        scale = _load_tensor_scale(im)
+        # the session's copy path; the in-place binding is not needed here
+        _, (det, cnt) = self._launch(s, (b, h, w), kw, lambda s, _: s(im, scale))
         # the tracker reads the session's det | count in place, on the stream that wrote them; then one copy of them
         # for the images that keep their predicted boxes (the session's buffers are reused by the next call)
         out, oc, tr = ts.update(det, cnt, [(h, w)] * b, reset_each=not persist)
@@ -642,15 +642,11 @@ class Model:
         imgsz = (imgsz, imgsz) if isinstance(imgsz, int) else tuple(imgsz)
         im = letterbox_batch(frames, imgsz, stride=int(self.model.stride.max()), device=dev)
         b, _, h, w = im.shape
-        kw = dict(half=args["half"], conf=args["conf"], iou=args["iou"], max_det=args["max_det"],
-                  agnostic=args["agnostic_nms"], classes=args["classes"], device=dev, fp8=args["fp8"], clip=False,
-                  streams=args["streams"], fp8_calibration=args["fp8_calibration"], augment=args["augment"])
+        kw = self._session_kw(args, dev, clip=False)
         ts = self._tracker_state(dev, cfg, args["max_det"], track_rows, b, persist, max_tracks)
         s = self.session(b, h, w, **kw)
         t1 = time.perf_counter()
-        det, cnt = s(im)
-        if self._stale(s):
-            det, cnt = self.session(b, h, w, **kw)(im)
+        _, (det, cnt) = self._launch(s, (b, h, w), kw, lambda s, _: s(im))
         # scale_boxes to each frame's own coordinates (rows past the count scale to garbage nobody reads), then the
         # same kernel over them with the frame's shape as the clip extent
         dets, counts = det.clone(), cnt.clone()

@@ -5,6 +5,9 @@ a batch costs one H2D/D2D copy into the static input buffer plus one graph
 launch.  Outputs are fixed-shape device buffers ``det [B, max_det, 6]``
 (x1, y1, x2, y2, conf, cls) and ``count [B]`` — the all-gather friendly
 layout used by the multi-GPU path.
+
+BatchSession is what the three session kinds share: a batch, possibly split into sub-batch plans, loaded through
+the staging buffers and replayed as one graph.  DetectOptions is the one record of a detection session's settings.
 """
 
 from __future__ import annotations
@@ -13,6 +16,7 @@ import ctypes as C
 import os
 import warnings
 import weakref
+from dataclasses import dataclass
 
 import torch
 
@@ -36,6 +40,45 @@ def default_streams(batch: int) -> int:
 # at conf 0.25: 645 at most) and the split's extra workgroups and merge cost +0.8 % of the step
 # (profiles/r05/r05_nms_per_image_ab.txt); validation's conf 0.001 keeps the split.
 PER_IMAGE_NMS_CONF = 0.1
+
+
+@dataclass(frozen=True)
+class DetectOptions:
+    """Every setting of a detection session (DetectSession, AugmentSession) besides its shape and placement, in the
+    order the constructors take them positionally.  Built once by the public constructor and handed as it is to the
+    sub-batch sessions; Model.session() derives its cache key from the fields, so a new field is in the key by
+    construction.  fp8 = True: every candidate conv in e4m3, a float in (0, 1): that share of the candidates' MACs,
+    least output-sensitive first (ydbl.quant.enable_fp8); fp8_calibration: an Fp8Calibration / its file, applied at
+    the first launch; loss = {"max_labels", "topk", "gains"[, "debug"]}: ydbl_detect_loss behind the head."""
+
+    dtype: torch.dtype = torch.float16
+    conf: float = 0.25
+    iou: float = 0.7
+    max_det: int = 300
+    multi_label: bool = False
+    agnostic: bool = False
+    classes: tuple | None = None
+    max_nms: int = 30000
+    max_wh: float = 7680
+    clip: bool = True
+    keep_pred: bool = False
+    use_graph: bool = True
+    nms: bool = True
+    fp8: bool | float = False
+    fp8_calibration: object = None
+    loss: dict | None = None
+
+    def __post_init__(self):
+        if self.classes is not None and type(self.classes) is not tuple:
+            object.__setattr__(self, "classes", tuple(self.classes))
+
+
+def _options(options, args, kw) -> DetectOptions:
+    if options is None:
+        return DetectOptions(*args, **kw)
+    if args or kw:
+        raise TypeError("options= takes the place of the single settings")
+    return options
 
 
 class BoundOutputs:
@@ -80,10 +123,96 @@ def _det_count(batch: int, max_det: int, dev):
     return flat[: batch * max_det * 6].view(batch, max_det, 6), flat[batch * max_det * 6:].view(torch.int32), flat
 
 
-class DetectSession:
-    """streams = k > 1: the batch is split into k contiguous sub-batches, each compiled into its own launch
+class BatchSession:
+    """A batch, possibly split, replayed as one graph: what DetectSession, AugmentSession and EmbedSession share.
+
+    streams = k > 1 (and batch >= k): the batch is split into k contiguous sub-batches (parallel.shard_bounds) --
+    ``bounds``, [(0, batch)] when unsplit -- each a session of the same kind in ``children`` (empty when unsplit) with
+    its own launch plan and buffers, writing its rows of the parent's shared outputs.  ``plans`` holds the plans in
+    row order, ``plan`` the first.  launch() replays them as ONE hipGraph -- a GraphRunner, or the k plans as the
+    branches of a BranchGraphRunner -- or, with use_graph=False, runs them eagerly, a split session's on one side
+    stream per plan (made on the first such launch) with a fork / join around them.
+
+    A subclass sets up its outputs, then calls _build(): that asks _child(i, a, b) for the session of rows a:b (built
+    onto slices of the outputs) when split, else _compile() for the session's own plan (which sets ``compiled``)."""
+
+    _bound = None
+    fp8 = fp8_ready = False  # only a DetectSession has e4m3 operands, calibrated at its first launch
+
+    def __init__(self, model, batch: int, h: int, w: int, dtype, use_graph, device, streams):
+        from ..parallel import shard_bounds
+
+        self.model, self.batch, self.h, self.w, self.dtype = model, batch, h, w, dtype
+        self.use_graph, self.device = use_graph, torch.device(device)
+        split = streams > 1 and batch >= streams
+        self.bounds = [shard_bounds(batch, streams, r) for r in range(streams)] if split else [(0, batch)]
+        self.children, self._graph, self._side = [], None, None
+
+    def _build(self):
+        if len(self.bounds) > 1:
+            self.children = [self._child(i, a, b) for i, (a, b) in enumerate(self.bounds)]
+            self.plans = [c.plan for c in self.children]
+        else:
+            self.plans = [self._compile()]
+        self.plan = self.plans[0]
+
+    @property
+    def parts(self):
+        """The sessions that own a plan, in row order: the children, or the unsplit session itself."""
+        return self.children or [self]
+
+    def load(self, x: torch.Tensor, scale: torch.Tensor | None = None):
+        """Copy a BCHW batch into the static input buffer(s) (LoadTensor semantics are the caller's); scale: a 0-dim
+        fp32 device tensor the batch is multiplied by on the way in (x * fp32(1/255) is what torch's GPU division by
+        255.0 computes, so no host sync is needed for it)."""
+        self._bound = None
+        parts = self.parts
+        shape = (self.batch, *parts[0].compiled.input.shape[1:])
+        if tuple(x.shape) != shape:
+            raise ValueError(f"input shape {tuple(x.shape)} != session shape {shape}")
+        for p, (a, b) in zip(parts, self.bounds):
+            xs = x[a:b] if self.children else x
+            if scale is None:
+                p.compiled.input.copy_(xs, non_blocking=True)
+            else:  # fp32 before the scale: x.float() / 255.0 as LoadTensor computes it (U/data/loaders.py:566)
+                torch.mul(xs if xs.dtype == torch.float32 else xs.float(), scale, out=p.compiled.input)
+
+    def launch(self):
+        if self.fp8 and not self.fp8_ready:  # (DetectSession) a given calibration, else the first batch calibrates
+            self.calibrate_fp8(calibration=self.fp8_calibration)  # (dynamic post-training quantization)
+        if self.use_graph:
+            g = self._graph
+            if g is None:  # every sub-batch plan a branch of one graph: one launch
+                g = self._graph = BranchGraphRunner(self.plans) if self.children else GraphRunner(self.plan)
+            g.replay()
+        elif self.children:  # eager: each sub-batch plan on its own stream, then join
+            dev = self.plan.buffers[0].device
+            if self._side is None:
+                self._side = [torch.cuda.Stream(dev) for _ in self.plans]
+            cur = torch.cuda.current_stream(dev)
+            for p, st in zip(self.plans, self._side):
+                st.wait_stream(cur)
+                with torch.cuda.stream(st):
+                    p.run()
+            for st in self._side:
+                cur.wait_stream(st)
+        else:
+            self.plan.run()
+
+    def __call__(self, x: torch.Tensor | None = None, scale: torch.Tensor | None = None):
+        if x is not None:
+            self.load(x, scale)
+        self.launch()
+        return self.outputs()
+
+
+class DetectSession(BatchSession):
+    """``DetectSession(model, batch, h, w, dtype, conf=..., ..., device=, streams=, gather_rows=)``: the settings, in
+    DetectOptions' order and under its names, or ``options=`` a ready record.
+
+    streams = k > 1: the batch is split into k contiguous sub-batches, each compiled into its own launch
     plan (own buffers) writing into slices of the shared det / count (/ pred) outputs; the k plans are captured
-    as k independent branches of ONE hipGraph (runtime.BranchGraphRunner; eager mode: one HIP stream per plan).
+    as k independent branches of ONE hipGraph (BatchSession; eager mode: one HIP stream per plan).
     At DBL-n/s sizes every launch is short and ramp/tail-bound, so two concurrent half-batch branches fill each
     other's gaps (scripts/stream_probe.py: DBL-n bs32 +10 %, DBL-s bs64 +14 %; one two-branch graph instead of
     two graphs on two streams a further +2.5 %, scripts/graph_branch_probe.py).
@@ -91,43 +220,36 @@ class DetectSession:
     sparse_box: the session runs the sparse box path (_sparse_box) -- its P3 / P4 box logits exist only
     in the 8 x 16 tiles that hold an NMS candidate of the last batch (see feats())."""
 
-    sparse_box = False
+    sparse_box = fused_candidates = False
+    records = loss = out_flat = None
 
-    def __init__(self, model, batch: int, h: int, w: int, dtype=torch.float16, conf=0.25, iou=0.7, max_det=300,
-                 multi_label=False, agnostic=False, classes=None, max_nms=30000, max_wh=7680, clip=True,
-                 keep_pred=False, use_graph=True, device="cuda", fp8=False, streams=1, gather_rows=None, nms=True,
-                 fp8_calibration=None, _outputs=None, _bind=None, loss=None):
-        if fp8 and dtype != torch.float16:
+    def __init__(self, model, batch: int, h: int, w: int, *args, device="cuda", streams=1, gather_rows=None,
+                 options=None, _outputs=None, _bind=None, **kw):
+        opt = _options(options, args, kw)
+        if opt.fp8 and opt.dtype != torch.float16:
             raise ValueError("fp8 operands run on the fp16 activation path (half=True)")
-        if fp8 and any(type(m).__name__ == "A2C2f" for m in model.modules()):
+        if opt.fp8 and any(type(m).__name__ == "A2C2f" for m in model.modules()):
             raise NotImplementedError("fp8=True on a model with A2C2f: no calibration record exists for the "
                                       "area-attention blocks")
-        self.model, self.batch, self.h, self.w, self.dtype = model, batch, h, w, dtype
-        self.fp8, self.fp8_ready = bool(fp8), False
-        self.fp8_calibration = fp8_calibration  # an Fp8Calibration / its file, applied at the first launch
-        # fp8=True: every candidate conv in e4m3; fp8=<float in (0, 1)>: that share of the candidates'
-        # MACs, least output-sensitive first (ydbl.quant.enable_fp8)
-        self.fp8_fraction = float(fp8) if not isinstance(fp8, bool) and 0 < float(fp8) < 1 else 1.0
-        self.conf, self.iou, self.max_det = float(conf), float(iou), int(max_det)
-        self.children = []
-        self.records = None
-        # loss = {"max_labels", "topk", "gains"[, "debug"]}: ydbl_detect_loss behind the head (_emit_loss).  The loss
-        # normalises by the whole batch's target scores, so the batch stays one plan, and it reads every level's box
-        # logits, so the levels stay dense (no sparse box path)
-        self.loss = None
-        if loss is not None:
+        # loss: ydbl_detect_loss behind the head (_emit_loss).  The loss normalises by the whole batch's target scores,
+        # so the batch stays one plan, and it reads every level's box logits, so the levels stay dense (no sparse box
+        # path)
+        if opt.loss is not None:
             if gather_rows is not None:
                 raise NotImplementedError("loss is not implemented for the batch-sharded predictor (gather_rows)")
             streams = 1
+        self._init_detect(model, batch, h, w, opt, device, streams)
+        fp8 = opt.fp8
+        self.fp8_fraction = float(fp8) if not isinstance(fp8, bool) and 0 < float(fp8) < 1 else 1.0
         # predict()'s in-place path (launch_bound): binding slot 0 is the session's own staging buffer (load()), slots
         # 1 and 2 alternate between predict() calls, each with its own graph (LoadTensor maximum + the plans) and its
         # own det | count outputs, kept until the slot comes round again (then copied if its Results still live)
-        self._bound = None  # the last tensor launch_bound() read (introspection)
         self._calls, self._slot_ptrs, self._pgraph, self._pout, self._pheld = 0, {}, {}, {}, {}
         self._max_work = {}  # per binding slot: the batch-max kernel's tickets are reset by its last block
         # the last launch_bound() replay (the slots share the plans' activation buffers): its stream and, per slot, an
         # event recorded after it -- a call from another stream waits for it, detach() waits for its slot's
         self._last_stream, self._slot_ev = None, {}
+        A = sum((h // int(st)) * (w // int(st)) for st in model.model[-1].stride.tolist())
         if _outputs is None and gather_rows is not None:
             # one record per image [det (max_det*6 fp32) | count (int32) | pad]: the boxes and counts of a batch-
             # sharded predict leave the GPU in ONE all-gather (ydbl.parallel); rows >= batch stay empty padding
@@ -136,92 +258,129 @@ class DetectSession:
             if gather_rows < batch:
                 raise ValueError(f"gather_rows {gather_rows} < batch {batch}")
             self.records = torch.zeros((gather_rows, record_width(self.max_det)), dtype=torch.float32,
-                                       device=torch.device(device))
+                                       device=self.device)
             det_v, cnt_v = record_views(self.records[:batch], self.max_det)
-            nc_ = model.model[-1].nc
-            A_ = sum((h // int(st)) * (w // int(st)) for st in model.model[-1].stride.tolist())
-            _outputs = (det_v, cnt_v,
-                        torch.empty((batch, 4 + nc_, A_), dtype=torch.float32, device=device) if keep_pred else None)
-        if streams > 1 and batch >= streams:
-            self._init_split(model, batch, h, w, dtype, conf, iou, max_det, multi_label, agnostic, classes, max_nms,
-                             max_wh, clip, keep_pred, use_graph, device, fp8, streams, nms, _outputs)
-            return
-        if _bind is None:  # a top-level session owns the binding slots (a split session's children get views)
-            self.bind_ptrs = torch.empty((3, 1), dtype=torch.int64, device=torch.device(device))
-            self.bind_amax = torch.zeros((3, 1), dtype=torch.float32, device=torch.device(device))
-            _bind = (self.bind_ptrs[0], self.bind_amax[0])
-        cm = model.compile(batch, h, w, dtype, device=device, bind=_bind)
-        self.compiled = cm
-        plan: Plan = cm.plan
-        det = cm.detect
-        nc = det.nc
-        multi_label = bool(multi_label) and nc > 1
-        A = sum(lv.h * lv.w for lv in cm.levels)
-        self.A, self.nc = A, nc
-        cap = A * nc if multi_label else A
-        dev = plan.device
-        self.cand_box = torch.empty((batch, cap, 4), dtype=torch.float32, device=dev)
-        self.cand_score = torch.empty((batch, cap), dtype=torch.float32, device=dev)
-        self.cand_cls = torch.empty((batch, cap), dtype=torch.int32, device=dev)
-        self.cand_idx = torch.empty((batch, cap), dtype=torch.int32, device=dev)
-        self.cand_count = torch.zeros((batch,), dtype=torch.int32, device=dev)
-        self.out_flat = None
-        if _outputs is not None:  # slices of a split session's shared outputs
+            _outputs = (det_v, cnt_v, torch.empty((batch, 4 + self.nc, A), dtype=torch.float32, device=device)
+                        if opt.keep_pred else None)
+        if _outputs is not None:  # record rows, or slices of a split session's shared outputs
             self.det, self.count, self.pred = _outputs
-        else:
-            self.pred = torch.empty((batch, 4 + nc, A), dtype=torch.float32, device=dev) if keep_pred else None
-            self.det, self.count, self.out_flat = _det_count(batch, self.max_det, dev)
-        self.classes_t = (torch.tensor(list(classes), dtype=torch.int32, device=dev) if classes is not None else None)
-        ws = torch.zeros(int(_lib.lib.ydbl_nms_workspace(batch, cap, max_nms)), dtype=torch.uint8, device=dev)  # zero-filled once (include/ydbl.h)
-        plan.buffers += [self.cand_box, self.cand_score, self.cand_cls, self.cand_idx, self.cand_count, self.det,
-                         self.count, ws]
-        boxes = (View * 3)(*[lv.cslice(0, 64).struct() for lv in cm.levels])
-        clss = (View * 3)(*[lv.cslice(64, nc).struct() for lv in cm.levels])
-        strides = (C.c_float * 3)(*[float(s) for s in det.stride.tolist()])
-        dd = DecodeDesc(boxes, clss, len(cm.levels), nc, strides, self.conf, int(multi_label),
-                        self.classes_t.data_ptr() if self.classes_t is not None else None,
-                        len(self.classes_t) if self.classes_t is not None else 0,
-                        self.pred.data_ptr() if self.pred is not None else None,
-                        self.cand_box.data_ptr(), self.cand_score.data_ptr(), self.cand_cls.data_ptr(),
-                        self.cand_idx.data_ptr(), self.cand_count.data_ptr(), cap)
+        elif len(self.bounds) > 1:
+            self._alloc_outputs(A)
+        self._bind = _bind
+        if _bind is None:  # a top-level session owns the binding slots (a split session's children get views): per
+            # slot one batch-pointer word per sub-batch plan and one batch maximum for all (launch_bound())
+            self.bind_ptrs = torch.empty((3, len(self.bounds)), dtype=torch.int64, device=self.device)
+            self.bind_amax = torch.zeros((3, 1), dtype=torch.float32, device=self.device)
+        self._build()
+        if self.children:
+            self.A = self.children[0].A
+            self.fused_candidates = all(c.fused_candidates for c in self.children)
+            self.sparse_box = all(c.sparse_box for c in self.children)
+        if _bind is None:
+            own = torch.tensor([p.compiled.input.data_ptr() for p in self.parts], dtype=torch.int64)
+            self.bind_ptrs.copy_(own.expand(3, -1))
+
+    def _init_detect(self, model, batch, h, w, opt: DetectOptions, device, streams):
+        """What every detection session has, binding or not: the record and the attributes read from outside."""
+        BatchSession.__init__(self, model, batch, h, w, opt.dtype, opt.use_graph, device, streams)
+        self.opt = opt
+        self.fp8, self.fp8_ready, self.fp8_calibration = bool(opt.fp8), False, opt.fp8_calibration
+        self.conf, self.iou, self.max_det = float(opt.conf), float(opt.iou), int(opt.max_det)
+        self.nc = model.model[-1].nc
+        self.det = self.count = self.pred = None
+
+    def _alloc_outputs(self, A: int):
+        self.det, self.count, self.out_flat = _det_count(self.batch, self.max_det, self.device)
+        self.pred = (torch.empty((self.batch, 4 + self.nc, A), dtype=torch.float32, device=self.device)
+                     if self.opt.keep_pred else None)
+
+    def _child(self, i: int, a: int, b: int):
+        outs = (self.det[a:b], self.count[a:b], self.pred[a:b] if self.pred is not None else None)
+        return DetectSession(self.model, b - a, self.h, self.w, device=self.device, options=self.opt, _outputs=outs,
+                             _bind=(self.bind_ptrs[0, i:i + 1], self.bind_amax[0]))
+
+    def _compile(self) -> Plan:
+        opt = self.opt
+        bind = self._bind or (self.bind_ptrs[0], self.bind_amax[0])
+        cm = self.compiled = self.model.compile(self.batch, self.h, self.w, self.dtype, device=self.device, bind=bind)
+        plan = cm.plan
+        self.A = sum(lv.h * lv.w for lv in cm.levels)
+        if self.det is None:
+            self._alloc_outputs(self.A)
+        self._init_tail(plan, self.A)
+        dd = self._decode_desc(cm.levels)
         # No decode pass when every level's class conv is the tail of a DWConv -> Conv1x1 launch (DBL-n, nc <= 4,
         # fp16) and no prediction tensor is wanted: those launches emit the candidates themselves (_fuse_candidates)
         self.fused_candidates = self.pred is None and self._fuse_candidates(plan, cm.levels, dd)
         # The sparse box path on top of that (predict thresholds, fp16 operands only: the fp8 calibration reads
         # feats(), and below PER_IMAGE_NMS_CONF most tiles hold a candidate): _sparse_box
-        self.sparse_box = bool(loss is None and self.fused_candidates and nms and not self.fp8
+        self.sparse_box = bool(opt.loss is None and self.fused_candidates and opt.nms and not self.fp8
                                and self.conf >= PER_IMAGE_NMS_CONF
                                and not os.environ.get("YDBL_NO_SPARSE_BOX") and self._sparse_box(plan, cm.levels, dd))
         if not self.fused_candidates:
             plan.launch("ydbl_detect_decode", dd, what="Detect.decode", keep=[dd])
-        nd = NmsDesc(self.cand_box.data_ptr(), self.cand_score.data_ptr(), self.cand_cls.data_ptr(),
-                     self.cand_idx.data_ptr(), self.cand_count.data_ptr(), batch, cap, self.iou, self.max_det,
-                     int(max_nms), int(bool(agnostic)), float(max_wh), float(w) if clip else 0.0,
-                     float(h) if clip else 0.0, self.det.data_ptr(), self.count.data_ptr(), ws.data_ptr(),
-                     self.det.stride(0), self.count.stride(0), int(self.conf >= PER_IMAGE_NMS_CONF))
-        if nms:  # nms=False: forward + decode only (DetectionModel.forward -> (y, feats))
-            plan.launch("ydbl_nms", nd, what="NMS", keep=[nd])
-        if loss is not None:
-            self._emit_loss(plan, cm, boxes, clss, loss)
-        self.plan = plan
-        self.plans = [plan]
-        self.use_graph = use_graph
-        self._graph = None
-        if hasattr(self, "bind_ptrs"):
-            self._init_slots()
+        self._emit_nms(plan)
+        if opt.loss is not None:
+            self._emit_loss(plan, cm, dd, opt.loss)
+        return plan
 
-    def _emit_loss(self, plan: Plan, cm, boxes, clss, cfg: dict):
+    # ------------------------------------------------------------------ the detection tail
+    def _init_tail(self, plan: Plan, A: int):
+        """The buffers behind the head, for A anchors per image: the candidate lists (cap = A, x nc multi-label) the
+        decode fills and the NMS reads, the ``classes`` filter and the NMS workspace, zero-filled once
+        (include/ydbl.h)."""
+        batch, dev = self.batch, plan.device
+        self.multi_label = bool(self.opt.multi_label) and self.nc > 1
+        cap = self.cap = A * self.nc if self.multi_label else A
+        self.cand_box = torch.empty((batch, cap, 4), dtype=torch.float32, device=dev)
+        self.cand_score = torch.empty((batch, cap), dtype=torch.float32, device=dev)
+        self.cand_cls = torch.empty((batch, cap), dtype=torch.int32, device=dev)
+        self.cand_idx = torch.empty((batch, cap), dtype=torch.int32, device=dev)
+        self._cand_count = torch.zeros((batch,), dtype=torch.int32, device=dev)
+        classes = self.opt.classes
+        self.classes_t = torch.tensor(list(classes), dtype=torch.int32, device=dev) if classes is not None else None
+        self._nms_ws = torch.zeros(int(_lib.lib.ydbl_nms_workspace(batch, cap, self.opt.max_nms)), dtype=torch.uint8,
+                                   device=dev)
+        plan.buffers += [self.cand_box, self.cand_score, self.cand_cls, self.cand_idx, self._cand_count, self.det,
+                         self.count, self._nms_ws]
+
+    def _decode_desc(self, levels) -> DecodeDesc:
+        """The decode of one forward's levels into the candidate lists (and ``pred``)."""
+        nc, ct = self.nc, self.classes_t
+        boxes = (View * 3)(*[lv.cslice(0, 64).struct() for lv in levels])
+        clss = (View * 3)(*[lv.cslice(64, nc).struct() for lv in levels])
+        strides = (C.c_float * 3)(*[float(s) for s in self.model.model[-1].stride.tolist()])
+        return DecodeDesc(boxes, clss, len(levels), nc, strides, self.conf, int(self.multi_label),
+                          ct.data_ptr() if ct is not None else None, len(ct) if ct is not None else 0,
+                          self.pred.data_ptr() if self.pred is not None else None,
+                          self.cand_box.data_ptr(), self.cand_score.data_ptr(), self.cand_cls.data_ptr(),
+                          self.cand_idx.data_ptr(), self._cand_count.data_ptr(), self.cap)
+
+    def _emit_nms(self, plan: Plan):
+        """ydbl_nms over the candidate lists into det / count; nms=False: forward + decode only
+        (DetectionModel.forward -> (y, feats))."""
+        if not self.opt.nms:
+            return
+        opt, h, w = self.opt, self.h, self.w
+        nd = NmsDesc(self.cand_box.data_ptr(), self.cand_score.data_ptr(), self.cand_cls.data_ptr(),
+                     self.cand_idx.data_ptr(), self._cand_count.data_ptr(), self.batch, self.cap, self.iou, self.max_det,
+                     int(opt.max_nms), int(bool(opt.agnostic)), float(opt.max_wh), float(w) if opt.clip else 0.0,
+                     float(h) if opt.clip else 0.0, self.det.data_ptr(), self.count.data_ptr(), self._nms_ws.data_ptr(),
+                     self.det.stride(0), self.count.stride(0), int(self.conf >= PER_IMAGE_NMS_CONF))
+        plan.launch("ydbl_nms", nd, what="NMS", keep=[nd])
+
+    def _emit_loss(self, plan: Plan, cm, dd: DecodeDesc, cfg: dict):
         """ydbl_detect_loss as the plan's last step, reading the level buffers in place: self.loss (utils.loss
         LossBuffers) holds gt [B, max_labels, 5] -- refilled by load_labels() before a replay, like the input -- and
         the outputs loss [3], target_scores_sum, per_image [B, 3]."""
         from ..utils.loss import MAX_LABELS, LossBuffers, loss_gains
 
-        det = cm.detect
-        self.loss = LossBuffers(list(boxes)[:len(cm.levels)], list(clss)[:len(cm.levels)], det.stride.tolist(), det.nc,
+        det, nl = cm.detect, len(cm.levels)
+        self.loss = LossBuffers(list(dd.box)[:nl], list(dd.cls)[:nl], det.stride.tolist(), det.nc,
                                 cfg.get("gains") or loss_gains(self.model), cfg.get("max_labels", MAX_LABELS),
                                 cfg.get("topk", 10), plan.device, debug=bool(cfg.get("debug")), reg_max=det.reg_max)
         plan.buffers += self.loss.tensors()
-        plan.launch("ydbl_detect_loss", self.loss.desc, what="Detect.loss", keep=[self.loss])
+        plan.launch("ydbl_detect_loss", self.loss.desc, what="Detect.loss", keep=[self.loss, dd])
 
     def load_labels(self, gt: torch.Tensor):
         """Refill the loss step's label buffer from a padded host / device tensor [B, max_labels, 5] (utils.loss
@@ -307,53 +466,12 @@ class DetectSession:
         plan.steps = steps
         return True
 
-    def _init_split(self, model, batch, h, w, dtype, conf, iou, max_det, multi_label, agnostic, classes, max_nms,
-                    max_wh, clip, keep_pred, use_graph, device, fp8, streams, nms, outputs):
-        from ..parallel import shard_bounds
-
-        dev = torch.device(device)
-        det = model.model[-1]
-        nc = det.nc
-        A = sum((h // int(s)) * (w // int(s)) for s in det.stride.tolist())
-        self.out_flat = None
-        if outputs is not None:
-            self.det, self.count, self.pred = outputs
-        else:
-            self.det, self.count, self.out_flat = _det_count(batch, self.max_det, dev)
-            self.pred = torch.empty((batch, 4 + nc, A), dtype=torch.float32, device=dev) if keep_pred else None
-        self.bounds = [shard_bounds(batch, streams, r) for r in range(streams)]
-        # per binding slot: one batch-pointer word per sub-batch plan, one batch maximum for all (launch_bound())
-        self.bind_ptrs = torch.empty((3, streams), dtype=torch.int64, device=dev)
-        self.bind_amax = torch.zeros((3, 1), dtype=torch.float32, device=dev)
-        for i, (a, b) in enumerate(self.bounds):
-            outs = (self.det[a:b], self.count[a:b], self.pred[a:b] if keep_pred else None)
-            self.children.append(DetectSession(model, b - a, h, w, dtype, conf, iou, max_det, multi_label, agnostic,
-                                               classes, max_nms, max_wh, clip, keep_pred, use_graph, device, fp8,
-                                               nms=nms, _outputs=outs,
-                                               _bind=(self.bind_ptrs[0, i:i + 1], self.bind_amax[0])))
-        self.streams = [torch.cuda.Stream(dev) for _ in self.children]
-        self.plans = [c.plan for c in self.children]
-        self.plan = self.plans[0]
-        self.use_graph = use_graph
-        self._graph = None  # all sub-batch plans as branches of one hipGraph (runtime.BranchGraphRunner)
-        self.nc, self.A = self.children[0].nc, self.children[0].A
-        self.sparse_box = all(c.sparse_box for c in self.children)
-        self._init_slots()
-
     @property
     def cand_count(self):
-        if self.children:
-            return torch.cat([c.cand_count for c in self.children])
-        return self._cand_count
-
-    @cand_count.setter
-    def cand_count(self, v):
-        self._cand_count = v
+        """Candidates per image of the last launch (a split session's: its sub-batches' counters, concatenated)."""
+        return torch.cat([c.cand_count for c in self.children]) if self.children else self._cand_count
 
     # ------------------------------------------------------------------ execution
-    def _own_inputs(self):
-        return [c.compiled.input.data_ptr() for c in (self.children or [self])]
-
     def can_bind(self, x: torch.Tensor) -> bool:
         """launch_bound() takes x: a contiguous fp32 tensor of the session's shape on its device, every sub-batch 16-byte
         aligned (the stem kernels' vector loads)."""
@@ -364,26 +482,18 @@ class DetectSession:
                 or (self.fp8 and not self.fp8_ready)):  # (an uncalibrated fp8 session calibrates on a loaded batch)
             return False
         per = 3 * self.h * self.w * 4
-        return all((x.data_ptr() + a * per) % 16 == 0 for a, _ in (self.bounds if self.children else [(0, 0)]))
-
-    def _owners(self):
-        return [c.compiled for c in self.children] if self.children else [self.compiled]
-
-    def _nms_descs(self):
-        return [st.args[0] for c in (self.children or [self]) for st in c.plan.steps if st.fn.__name__ == "ydbl_nms"]
-
-    def _init_slots(self):
-        own = torch.tensor(self._own_inputs(), dtype=torch.int64)
-        self.bind_ptrs.copy_(own.expand(self.bind_ptrs.shape[0], -1))
+        return all((x.data_ptr() + a * per) % 16 == 0 for a, _ in self.bounds)
 
     def _set_slot(self, k: int, det: torch.Tensor | None = None, count: torch.Tensor | None = None):
         """Point the plans' input-reading launches at binding slot k and their NMS outputs at det / count (default:
         the session's own), before a capture; the C-ABI copies both into the kernel arguments at launch."""
-        for i, cm in enumerate(self._owners()):  # slot 0: no binding, the plans read their own staging buffers
-            cm.set_bind(self.bind_ptrs[k, i:i + 1] if k else None, self.bind_amax[k])
+        parts = self.parts
+        for i, p in enumerate(parts):  # slot 0: no binding, the plans read their own staging buffers
+            p.compiled.set_bind(self.bind_ptrs[k, i:i + 1] if k else None, self.bind_amax[k])
         det = self.det if det is None else det
         count = self.count if count is None else count
-        for nd, (a, b) in zip(self._nms_descs(), self.bounds if self.children else [(0, self.batch)]):
+        nds = [st.args[0] for p in parts for st in p.plan.steps if st.fn.__name__ == "ydbl_nms"]
+        for nd, (a, b) in zip(nds, self.bounds):
             nd.out, nd.out_count = det[a:b].data_ptr(), count[a:b].data_ptr()
 
     def launch_bound(self, x: torch.Tensor) -> "BoundOutputs":
@@ -404,7 +514,7 @@ class DetectSession:
         if held is not None:
             held.detach()  # a live result of the call two back: copy it out of the slot before the slot is rewritten
         per = 3 * self.h * self.w * 4
-        ptrs = [x.data_ptr() + a * per for a, _ in (self.bounds if self.children else [(0, 0)])]
+        ptrs = [x.data_ptr() + a * per for a, _ in self.bounds]
         if ptrs != self._slot_ptrs.get(k):  # (the words keep their value from call to call for the same tensor)
             self.bind_ptrs[k].copy_(torch.tensor(ptrs, dtype=torch.int64), non_blocking=True)
             self._slot_ptrs[k] = ptrs
@@ -442,24 +552,6 @@ class DetectSession:
         self._bound = x
         return out
 
-    def load(self, x: torch.Tensor, scale: torch.Tensor | None = None):
-        """Copy a BCHW batch into the static input buffer (LoadTensor semantics are the caller's); scale: a 0-dim
-        fp32 device tensor the batch is multiplied by on the way in (x * fp32(1/255) is what torch's GPU division by
-        255.0 computes, so no host sync is needed for it)."""
-        self._bound = None
-        if self.children:
-            if tuple(x.shape[1:]) != (3, self.h, self.w) or x.shape[0] != self.batch:
-                raise ValueError(f"input shape {tuple(x.shape)} != session shape {(self.batch, 3, self.h, self.w)}")
-            for c, (a, b) in zip(self.children, self.bounds):
-                c.load(x[a:b], scale)
-            return
-        if tuple(x.shape) != tuple(self.compiled.input.shape):
-            raise ValueError(f"input shape {tuple(x.shape)} != session shape {tuple(self.compiled.input.shape)}")
-        if scale is None:
-            self.compiled.input.copy_(x, non_blocking=True)
-        else:  # fp32 before the scale: x.float() / 255.0 as LoadTensor computes it (U/data/loaders.py:566)
-            torch.mul(x if x.dtype == torch.float32 else x.float(), scale, out=self.compiled.input)
-
     def calibrate_fp8(self, x: torch.Tensor | None = None, fraction: float | None = None, calibration=None) -> int:
         """Switch the dense convs to e4m3 operands (ydbl.quant).  calibration (an ydbl.quant.Fp8Calibration or the
         path of one saved with .save()): its activation scales, bias corrections and layer set; else one measured
@@ -478,23 +570,20 @@ class DetectSession:
         frac = self.fp8_fraction if fraction is None else float(fraction)
         # one joint calibration over every sub-batch plan (ydbl.quant.enable_fp8): the same activation scales
         # and the same fp8 layer set for every image of the batch, whichever stream it runs on
-        owners = self.children or [self]
+        parts = self.parts
 
         def run_all():
-            for c in owners:
-                c.plan.run()
+            for p in self.plans:
+                p.run()
 
         def heads():
-            return [t for c in owners for t in c.compiled.feats()]
+            return [t for c in parts for t in c.compiled.feats()]
 
-        n = enable_fp8([c.plan for c in owners], run_all, fraction=frac, head=heads, calibration=calibration)
-        self.fp8_calibration = owners[0].plan.fp8_calibration
-        for c in owners:
-            c._graph = None  # descriptors changed: recapture
-            c.fp8_ready = True
-        self._graph = None
+        n = enable_fp8(self.plans, run_all, fraction=frac, head=heads, calibration=calibration)
+        self.fp8_calibration = self.plan.fp8_calibration
+        for c in (self, *parts):  # descriptors changed: recapture
+            c._graph, c.fp8_ready = None, True
         self._pgraph.clear()
-        self.fp8_ready = True
         return n
 
     @property
@@ -502,35 +591,7 @@ class DetectSession:
         """Share of the fp8 candidates' MACs switched to e4m3 (None before calibration)."""
         return getattr(self.plan, "fp8_mac_fraction", None)
 
-    def launch(self):
-        if self.fp8 and not self.fp8_ready:
-            # a given calibration, else the first batch calibrates (dynamic post-training quantization)
-            self.calibrate_fp8(calibration=self.fp8_calibration)
-        if self.children and self.use_graph:  # every sub-batch plan a branch of one graph: one launch
-            if self._graph is None:
-                self._graph = BranchGraphRunner(self.plans)
-            self._graph.replay()
-            return
-        if self.children:  # eager: each sub-batch plan on its own stream, then join
-            cur = torch.cuda.current_stream(self.det.device)
-            for c, st in zip(self.children, self.streams):
-                st.wait_stream(cur)
-                with torch.cuda.stream(st):
-                    c.launch()
-            for st in self.streams:
-                cur.wait_stream(st)
-            return
-        if self.use_graph:
-            if self._graph is None:
-                self._graph = GraphRunner(self.plan)
-            self._graph.replay()
-        else:
-            self.plan.run()
-
-    def __call__(self, x: torch.Tensor | None = None, scale: torch.Tensor | None = None):
-        if x is not None:
-            self.load(x, scale)
-        self.launch()
+    def outputs(self):
         return self.det, self.count
 
     def results(self):
@@ -599,91 +660,59 @@ class AugmentSession(DetectSession):
 
     all on one stream, captured as one hipGraph (use_graph): no host round trip between the passes.  streams = k
     splits the batch as DetectSession does, each sub-batch running its own three passes as one branch of the graph.
-    There is no in-place input binding (can_bind() is False: predict() takes the copy path) and no fp8 (the
-    calibration is per plan).  The NMS candidate capacity is A_tot (x nc multi-label): 15 049 at 640^2, above
-    ydbl_nms's 8192-candidate pair-matrix limit like the plain session's 8400, so its workspace per image is the
-    same ~9.1 MB (ydbl_nms_workspace: 16384 sort slots, 8 class-group lists, 8192 pair-matrix rows)."""
+    Takes DetectSession's settings (DetectOptions).  Not supported, and refused as such: in-place input binding
+    (can_bind() is False, so predict() takes the copy path, and launch_bound() raises ValueError), fp8 (the
+    calibration is per compiled plan: NotImplementedError from the constructor and from calibrate_fp8()) and loss
+    (the three passes have no single set of levels to score: ValueError from the constructor, and load_labels()
+    raises RuntimeError as on any session built without loss=).  The NMS candidate capacity is A_tot (x nc
+    multi-label): 15 049 at 640^2, above ydbl_nms's 8192-candidate pair-matrix limit like the plain session's 8400,
+    so its workspace per image is the same ~9.1 MB (ydbl_nms_workspace: 16384 sort slots, 8 class-group lists, 8192
+    pair-matrix rows)."""
 
-    def __init__(self, model, batch: int, h: int, w: int, dtype=torch.float16, conf=0.25, iou=0.7, max_det=300,
-                 multi_label=False, agnostic=False, classes=None, max_nms=30000, max_wh=7680, clip=True,
-                 keep_pred=False, use_graph=True, device="cuda", fp8=False, streams=1, nms=True, _outputs=None):
-        if fp8:
+    def __init__(self, model, batch: int, h: int, w: int, *args, device="cuda", streams=1, options=None,
+                 _outputs=None, **kw):
+        opt = _options(options, args, kw)
+        if opt.fp8:
             raise NotImplementedError("augment=True with fp8: the fp8 calibration is per compiled plan, and the "
                                       "augmented session runs three; use half=True")
-        self.model, self.batch, self.h, self.w, self.dtype = model, batch, h, w, dtype
-        self.fp8, self.fp8_ready, self.fp8_calibration = False, False, None
-        self.conf, self.iou, self.max_det = float(conf), float(iou), int(max_det)
-        self.children, self.records, self._bound, self._graph = [], None, None, None
-        self.use_graph = use_graph
-        dev = torch.device(device)
-        det = model.model[-1]
-        nc = det.nc
-        multi_label = bool(multi_label) and nc > 1
-        self.passes = augment_passes(h, w, det.stride.tolist())
-        A = self.passes[-1][7] + self.passes[-1][6] - self.passes[-1][5]
-        self.A, self.nc, self.out_flat = A, nc, None
+        if opt.loss is not None:
+            raise ValueError("augment=True with loss: the three augmented passes have no single set of levels to score")
+        self._init_detect(model, batch, h, w, opt, device, streams)
+        self.passes = augment_passes(h, w, model.model[-1].stride.tolist())
+        self.A = self.passes[-1][7] + self.passes[-1][6] - self.passes[-1][5]
         if _outputs is not None:  # slices of a split session's shared outputs
             self.det, self.count, self.pred = _outputs
         else:
-            self.pred = torch.empty((batch, 4 + nc, A), dtype=torch.float32, device=dev) if keep_pred else None
-            self.det, self.count, self.out_flat = _det_count(batch, self.max_det, dev)
-        if streams > 1 and batch >= streams:
-            from ..parallel import shard_bounds
+            self._alloc_outputs(self.A)
+        self._build()
 
-            self.bounds = [shard_bounds(batch, streams, r) for r in range(streams)]
-            for a, b in self.bounds:
-                outs = (self.det[a:b], self.count[a:b], self.pred[a:b] if keep_pred else None)
-                self.children.append(AugmentSession(model, b - a, h, w, dtype, conf, iou, max_det, multi_label,
-                                                    agnostic, classes, max_nms, max_wh, clip, keep_pred, use_graph,
-                                                    device, nms=nms, _outputs=outs))
-            self.streams = [torch.cuda.Stream(dev) for _ in self.children]
-            self.plans = [c.plan for c in self.children]
-            self.plan = self.plans[0]
-            return
+    def _child(self, i: int, a: int, b: int):
+        outs = (self.det[a:b], self.count[a:b], self.pred[a:b] if self.pred is not None else None)
+        return AugmentSession(self.model, b - a, self.h, self.w, device=self.device, options=self.opt, _outputs=outs)
+
+    def _compile(self) -> Plan:
         from .preprocess import SCALE_IMG_PAD
 
-        cms = [model.compile(batch, hp, wp, dtype, device=dev) for _, _, _, (hp, wp), *_ in self.passes]
+        batch, h, w, dev, A = self.batch, self.h, self.w, self.device, self.A
+        cms = [self.model.compile(batch, hp, wp, self.dtype, device=dev) for _, _, _, (hp, wp), *_ in self.passes]
         self.compiled_passes, self.compiled = cms, cms[0]  # (load() fills pass 0's staging buffer)
-        cap = A * nc if multi_label else A
-        self.cand_box = torch.empty((batch, cap, 4), dtype=torch.float32, device=dev)
-        self.cand_score = torch.empty((batch, cap), dtype=torch.float32, device=dev)
-        self.cand_cls = torch.empty((batch, cap), dtype=torch.int32, device=dev)
-        self.cand_idx = torch.empty((batch, cap), dtype=torch.int32, device=dev)
-        self.cand_count = torch.zeros((batch,), dtype=torch.int32, device=dev)
-        self.classes_t = (torch.tensor(list(classes), dtype=torch.int32, device=dev) if classes is not None else None)
-        ws = torch.zeros(int(_lib.lib.ydbl_nms_workspace(batch, cap, max_nms)), dtype=torch.uint8, device=dev)
-        plan = Plan(dev, dtype)
-        plan.buffers += [self.cand_box, self.cand_score, self.cand_cls, self.cand_idx, self.cand_count, self.det,
-                         self.count, ws]
+        plan = Plan(dev, self.dtype)
+        self._init_tail(plan, A)
         ch = cms[0].input.shape[1]
         for cm, (ratio, flip, (sh, sw), (hp, wp), *_) in zip(cms[1:], self.passes[1:]):
             sd = ScaleImgDesc(cms[0].input.data_ptr(), batch, ch, h, w, sh, sw, hp, wp, int(flip), SCALE_IMG_PAD,
                               cm.input.data_ptr())
             plan.launch("ydbl_scale_img", sd, what=f"scale_img {ratio}", keep=[sd])
-        strides = (C.c_float * 3)(*[float(s) for s in det.stride.tolist()])
         for i, (cm, (ratio, flip, _, _, A_i, a_lo, a_hi, pos)) in enumerate(zip(cms, self.passes)):
             if sum(lv.h * lv.w for lv in cm.levels) != A_i:
                 raise RuntimeError(f"pass {i}: the compiled levels hold {sum(lv.h * lv.w for lv in cm.levels)} "
                                    f"anchors, augment_passes() expects {A_i}")
             plan.steps += cm.plan.steps
-            boxes = (View * 3)(*[lv.cslice(0, 64).struct() for lv in cm.levels])
-            clss = (View * 3)(*[lv.cslice(64, nc).struct() for lv in cm.levels])
-            dd = DecodeDesc(boxes, clss, len(cm.levels), nc, strides, self.conf, int(multi_label),
-                            self.classes_t.data_ptr() if self.classes_t is not None else None,
-                            len(self.classes_t) if self.classes_t is not None else 0,
-                            self.pred.data_ptr() if self.pred is not None else None,
-                            self.cand_box.data_ptr(), self.cand_score.data_ptr(), self.cand_cls.data_ptr(),
-                            self.cand_idx.data_ptr(), self.cand_count.data_ptr(), cap)
+            dd = self._decode_desc(cm.levels)
             ga = DecodeAug(float(ratio), float(w) if flip else 0.0, a_lo, a_hi, pos, A, int(i > 0))
             plan.launch("ydbl_detect_decode_aug", dd, ga, what=f"Detect.decode pass {i}", keep=[dd, ga])
-        nd = NmsDesc(self.cand_box.data_ptr(), self.cand_score.data_ptr(), self.cand_cls.data_ptr(),
-                     self.cand_idx.data_ptr(), self.cand_count.data_ptr(), batch, cap, self.iou, self.max_det,
-                     int(max_nms), int(bool(agnostic)), float(max_wh), float(w) if clip else 0.0,
-                     float(h) if clip else 0.0, self.det.data_ptr(), self.count.data_ptr(), ws.data_ptr(),
-                     self.det.stride(0), self.count.stride(0), int(self.conf >= PER_IMAGE_NMS_CONF))
-        if nms:
-            plan.launch("ydbl_nms", nd, what="NMS", keep=[nd])
-        self.plan, self.plans = plan, [plan]
+        self._emit_nms(plan)
+        return plan
 
     def can_bind(self, x) -> bool:
         """Never: scale_img reads pass 0's staging buffer, so predict() takes the copy path."""
@@ -697,15 +726,15 @@ class AugmentSession(DetectSession):
         return None
 
 
-class EmbedSession:
+class EmbedSession(BatchSession):
     """``embed=[i, ...]``: pooled layer features instead of detections (Model.embed, U/engine/model.py:467-499;
     _predict_once's early return, U/nn/tasks.py:158-171).  The compiled plan stops at layer max(embed) -- no Detect
     branches, no decode, no NMS -- with one ydbl_global_avgpool behind each named layer; ``out [B, D]`` (D = the
     layers' channel counts summed, ascending layer order, plan dtype) is owned by the session and rewritten by the
     next call.
 
-    streams = k > 1 splits the batch into k contiguous sub-batches (parallel.shard_bounds, as DetectSession): one
-    plan per sub-batch, each writing its rows of the one shared ``out``, captured as the branches of ONE hipGraph
+    streams = k > 1 splits the batch into k contiguous sub-batches (BatchSession, as DetectSession): one plan per
+    sub-batch, each writing its rows of the one shared ``out``, captured as the branches of ONE hipGraph
     (runtime.BranchGraphRunner); streams == 1 replays one GraphRunner.  Every plan passes Plan.check_single_stream.
     The batch goes through the staging copy (load(), with LoadTensor's /255 rule as its scale argument); there is no
     in-place input binding (launch_bound) for these sessions."""
@@ -715,58 +744,24 @@ class EmbedSession:
         from ..nn.tasks import _propagate_shapes, normalize_embed
 
         self.embed = normalize_embed(embed, len(model.model))
-        self.model, self.batch, self.h, self.w, self.dtype = model, batch, h, w, dtype
-        self.use_graph, self._graph, self.children, self.bounds = use_graph, None, [], None
-        dev = torch.device(device)
-        if streams > 1 and batch >= streams:
-            from ..parallel import shard_bounds
-
-            self.bounds = [shard_bounds(batch, streams, r) for r in range(streams)]
-            # one [B, D] output, each sub-batch plan compiled onto its row slice
+        super().__init__(model, batch, h, w, dtype, use_graph, device, streams)
+        self.out = _out
+        if len(self.bounds) > 1 and _out is None:  # one [B, D] output, each sub-batch plan compiled onto its row slice
             shapes = _propagate_shapes(list(model.model)[: self.embed[-1] + 1], 1, h, w, model.yaml["ch"])
-            self.dim = sum(shapes[i][3] for i in self.embed)
-            self.out = torch.empty((batch, self.dim), dtype=dtype, device=dev) if _out is None else _out
-            self.children = [EmbedSession(model, b - a, h, w, dtype, self.embed, dev, use_graph=use_graph,
-                                          _out=self.out[a:b]) for a, b in self.bounds]
-            self.streams = [torch.cuda.Stream(dev) for _ in self.children]
-            self.plans = [c.plan for c in self.children]
-            self.plan = self.plans[0]
-            return
-        cm = model.compile(batch, h, w, dtype, device=dev, embed=self.embed, embed_out=_out)
-        self.compiled, self.plan, self.plans = cm, cm.plan, [cm.plan]
-        self.out, self.dim = cm.embed_out, cm.embed_out.shape[1]
-        self.plan.check_single_stream()
+            self.out = torch.empty((batch, sum(shapes[i][3] for i in self.embed)), dtype=dtype, device=self.device)
+        self._build()
+        self.dim = self.out.shape[1]
 
-    def load(self, x: torch.Tensor, scale: torch.Tensor | None = None):
-        """Copy a BCHW batch into the staging buffer(s), multiplied by `scale` on the way (DetectSession.load)."""
-        if tuple(x.shape) != (self.batch, 3, self.h, self.w):
-            raise ValueError(f"input shape {tuple(x.shape)} != session shape {(self.batch, 3, self.h, self.w)}")
-        if self.children:
-            for c, (a, b) in zip(self.children, self.bounds):
-                c.load(x[a:b], scale)
-        elif scale is None:
-            self.compiled.input.copy_(x, non_blocking=True)
-        else:
-            torch.mul(x if x.dtype == torch.float32 else x.float(), scale, out=self.compiled.input)
+    def _child(self, i: int, a: int, b: int):
+        return EmbedSession(self.model, b - a, self.h, self.w, self.dtype, self.embed, self.device,
+                            use_graph=self.use_graph, _out=self.out[a:b])
 
-    def launch(self):
-        if self.use_graph:
-            if self._graph is None:
-                self._graph = BranchGraphRunner(self.plans) if self.children else GraphRunner(self.plan)
-            self._graph.replay()
-        elif self.children:  # eager: each sub-batch plan on its own stream, then join
-            cur = torch.cuda.current_stream(self.out.device)
-            for c, st in zip(self.children, self.streams):
-                st.wait_stream(cur)
-                with torch.cuda.stream(st):
-                    c.plan.run()
-            for st in self.streams:
-                cur.wait_stream(st)
-        else:
-            self.plan.run()
+    def _compile(self) -> Plan:
+        cm = self.compiled = self.model.compile(self.batch, self.h, self.w, self.dtype, device=self.device,
+                                                embed=self.embed, embed_out=self.out)
+        self.out = cm.embed_out
+        cm.plan.check_single_stream()
+        return cm.plan
 
-    def __call__(self, x: torch.Tensor | None = None, scale: torch.Tensor | None = None) -> torch.Tensor:
-        if x is not None:
-            self.load(x, scale)
-        self.launch()
+    def outputs(self) -> torch.Tensor:
         return self.out

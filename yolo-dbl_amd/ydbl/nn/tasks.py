@@ -276,21 +276,9 @@ class DetectionModel(nn.Module):
             raise TypeError(f"input dtype {x.dtype}: float32 or float16 (half) expected")
         if x.shape[1] != self.yaml["ch"]:
             raise ValueError(f"input has {x.shape[1]} channels, the model {self.yaml['ch']}")
-        b, _, h, w = x.shape
         if embed:  # _predict_once's early return (U/nn/tasks.py:168-171): torch.unbind(torch.cat(embeddings, 1), 0)
-            s = self._forward_session(b, h, w, x.dtype == torch.float16, x.device, embed=embed)
-            out = s(x.float())
-            sig = weights_signature(self)
-            if sig != s.wsig:
-                s = self._forward_session(b, h, w, x.dtype == torch.float16, x.device, fresh=sig, embed=embed)
-                out = s(x.float())
-            return out.to(x.dtype, copy=True).unbind(0)
-        s = self._forward_session(b, h, w, x.dtype == torch.float16, x.device, augment=augment)
-        s(x.float())
-        sig = weights_signature(self)  # checked while the graph runs
-        if sig != s.wsig:  # weights edited since the plan was compiled: rebuild, run again
-            s = self._forward_session(b, h, w, x.dtype == torch.float16, x.device, fresh=sig, augment=augment)
-            s(x.float())
+            return self._run(x, embed=embed)[1].to(x.dtype, copy=True).unbind(0)
+        s, _ = self._run(x, augment=augment)
         y = s.pred.to(x.dtype, copy=True)
         if augment:
             return y, None
@@ -328,20 +316,28 @@ class DetectionModel(nn.Module):
             raise TypeError(f"input dtype {x.dtype}: float32 or float16 (half) expected")
         if x.shape[1] != self.yaml["ch"]:
             raise ValueError(f"input has {x.shape[1]} channels, the model {self.yaml['ch']}")
-        half = x.dtype == torch.float16
-        s = self._forward_session(b, h, w, half, x.device, loss=True)
-        s.load_labels(gt)
-        s(x.float())
-        sig = weights_signature(self)
-        if sig != s.wsig:  # weights edited since the plan was compiled: rebuild, run again
-            s = self._forward_session(b, h, w, half, x.device, fresh=sig, loss=True)
-            s.load_labels(gt)
-            s(x.float())
+        s, _ = self._run(x, gt, loss=True)
         items = s.loss.loss.clone()
         return items.sum() * b, items
 
+    def _run(self, x, labels=None, **kw):
+        """One launch of x -- `labels` refilled into a loss session's buffer first -- on the compiled session of its
+        shape and dtype (_forward_session(**kw)).  The weights' signature is checked while the graph runs; when they
+        were edited since the plan was compiled, the session is rebuilt and run again.  Returns (session, outputs)."""
+        b, _, h, w = x.shape
+        fresh = None
+        for _ in range(2):
+            s = self._forward_session(b, h, w, x.dtype == torch.float16, x.device, fresh=fresh, **kw)
+            if labels is not None:
+                s.load_labels(labels)
+            out = s(x.float())
+            fresh = weights_signature(self)
+            if fresh == s.wsig:
+                break
+        return s, out
+
     def _forward_session(self, b, h, w, half, device, fresh=None, augment=False, embed=None, loss=False):
-        from ..engine.session import AugmentSession, DetectSession, EmbedSession, default_streams
+        from ..engine.session import AugmentSession, DetectOptions, DetectSession, EmbedSession, default_streams
 
         cache = self.__dict__.setdefault("_fwd_sessions", {})
         # compiled plans hold the routing of the YDBL_* switches at build time (part of the key) and BN-folded
@@ -354,17 +350,16 @@ class DetectionModel(nn.Module):
         if s is None:
             while len(cache) >= self.MAX_FORWARD_SESSIONS:
                 cache.pop(next(iter(cache)))
+            dtype = torch.float16 if half else torch.float32
             with torch.cuda.device(device):
                 if embed:
-                    s = EmbedSession(self, b, h, w, torch.float16 if half else torch.float32, embed, device=device,
-                                     streams=default_streams(b))
-                elif loss:  # forward + decode + ydbl_detect_loss on dense levels, one plan (the batch's normaliser)
-                    s = DetectSession(self, b, h, w, torch.float16 if half else torch.float32, keep_pred=True,
-                                      nms=False, device=device, streams=1, loss={"max_labels": self.MAX_LABELS})
-                else:
-                    s = (AugmentSession if augment else DetectSession)(
-                        self, b, h, w, torch.float16 if half else torch.float32, keep_pred=True, nms=False,
-                        device=device, streams=default_streams(b))
+                    s = EmbedSession(self, b, h, w, dtype, embed, device=device, streams=default_streams(b))
+                else:  # forward + decode, no NMS; loss: + ydbl_detect_loss on dense levels, one plan (a loss session
+                    # never splits: one normaliser for the batch)
+                    opt = DetectOptions(dtype, keep_pred=True, nms=False,
+                                        loss={"max_labels": self.MAX_LABELS} if loss else None)
+                    s = (AugmentSession if augment else DetectSession)(self, b, h, w, device=device,
+                                                                       streams=default_streams(b), options=opt)
             s.wsig = weights_signature(self)
         cache[key] = s  # most recently used last
         return s
