@@ -1,7 +1,8 @@
 """Per-kernel parity on the MI355X: each HIP op vs the oracle / a torch fp32 CPU reference.
 
 Tolerances: fp32 path (exact-f32 MFMA, fp32 VALU) rtol 1e-5-ish, written per test;
-fp16 path: fp16 storage + fp32 accumulation, ~1e-2 relative.  NMS is bit-exact.
+fp16 path: fp16 storage + fp32 accumulation, ~1e-2 relative here (a smoke bound: the conv kernels' fp16 outputs are held
+to rounding accuracy, in fp16 ulps against float64, by tests/test_gpu_fp16_error.py).  NMS is bit-exact.
 """
 
 import numpy as np
