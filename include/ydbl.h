@@ -211,8 +211,15 @@ int ydbl_dwconv2d_nhwc(const ydbl_dwconv_desc* d, void* stream);
 
 /* Two chained depthwise convs, d1.x == d0.y: LSKblock's conv0 (5x5) -> conv_spatial (7x7, dil 3)
  * (modules_attention/LSKA.py:40-41).  One launch with the whole map in LDS when H*W <= 512 (the P5
- * maps at 640), bit-identical to the two ydbl_dwconv2d_nhwc launches it falls back to otherwise. */
+ * maps at 640), bit-identical to the two ydbl_dwconv2d_nhwc launches it falls back to otherwise.
+ * fp16 without activation, pads 2 and 9, and both zero-padded maps ((H+4)(W+4) + (H+18)(W+18) pixels x 16
+ * channels) within 80 KiB of LDS run a kernel that keeps the padded taps as fma(0, w, acc) terms instead of
+ * skipping them: bit-identical for FINITE WEIGHTS (an infinite or NaN tap turns the padded border into NaN);
+ * YDBL_DW_PAIR_OLD=1 (read per launch) keeps the tap-skipping kernel.
+ * ydbl_dwconv2d_pair_route: what the call above would launch for these descriptors, without launching:
+ * 0 the two ydbl_dwconv2d_nhwc launches, 1 the tap-skipping kernel, 2 the padded-map kernel; -1 a NULL descriptor. */
 int ydbl_dwconv2d_pair_nhwc(const ydbl_dwconv_desc* d0, const ydbl_dwconv_desc* d1, void* stream);
+int ydbl_dwconv2d_pair_route(const ydbl_dwconv_desc* d0, const ydbl_dwconv_desc* d1);
 
 /* Input binding: the batch a graph-captured plan reads, chosen when the plan RUNS (YOLO.predict on a device tensor
  * without a staging copy).  When a kernel below gets a non-NULL `bind`, it takes the NCHW fp32 batch pointer from the

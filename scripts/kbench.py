@@ -161,7 +161,20 @@ def case_dysample(B, c, H):
     return f"dysample {c}@{H} bs{B}", build
 
 
-CASES = [case_dsc3k(16, 128, 20), case_hg(16, 64, 40), case_hg(16, 128, 40), case_dysample(16, 128, 40), case_dysample(16, 256, 20), case_stem2(16), case_box3(16, 64, 80), case_box3(16, 128, 40), case_pair(16, 64, 64, 80),
+def case_dwpair(B, c, H):
+    """LSKblock's dw 5x5 -> dw 7x7 dil 3 as one launch (YDBL_DW_PAIR_OLD=1: the tap-skipping kernel)."""
+    def build():
+        p = Plan(torch.device("cuda"), torch.float16)
+        x = p.alloc(B, H, H, c)
+        rnd(p, x)
+        c0 = torch.nn.Conv2d(c, c, 5, padding=2, groups=c)
+        c1 = torch.nn.Conv2d(c, c, 7, padding=9, groups=c, dilation=3)
+        M.emit_dw_pair(p, c0, c1, x)
+        return p
+    return f"dwpair {c}@{H} bs{B}", build
+
+
+CASES = [case_dsc3k(16, 128, 20), case_hg(16, 64, 40), case_hg(16, 128, 40), case_dysample(16, 128, 40), case_dysample(16, 256, 20), case_dwpair(16, 256, 20), case_dwpair(32, 256, 20), case_stem2(16), case_box3(16, 64, 80), case_box3(16, 128, 40), case_pair(16, 64, 64, 80),
          case_pair(16, 64, 64, 80, True), case_pair(16, 128, 64, 40), case_pair(16, 256, 64, 20),
          case_dsconv(16, 128, 128, 3, 2, 80, 80), case_conv(16, 16, 32, 3, 2, 320, 320),
          case_conv(16, 32, 64, 3, 2, 160, 160), case_bneck(16, 32, 160),case_gate(16, 8, 8, 64), case_gate(16, 40, 40, 64),

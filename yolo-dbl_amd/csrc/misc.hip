@@ -553,6 +553,10 @@ static DView<const T> cview(const ydbl_view* v) {
 
 static unsigned nblk(int64_t n) { return (unsigned)cdiv(n, 256); }
 
+// dw_pair.hip: the fp16 no-activation form of the fused pair, and whether a checked pair geometry is its own
+bool dw_pair_fast_ok(const ydbl_dwconv_desc* d0, const ydbl_dwconv_desc* d1);
+int dw_pair_fast_launch(const ydbl_dwconv_desc* d0, const ydbl_dwconv_desc* d1, hipStream_t s);
+
 }  // namespace ydbl
 
 using namespace ydbl;
@@ -592,10 +596,10 @@ extern "C" int ydbl_dwconv2d_nhwc(const ydbl_dwconv_desc* d, void* stream) {
   return check_launch("ydbl_dwconv2d_nhwc");
 }
 
-extern "C" int ydbl_dwconv2d_pair_nhwc(const ydbl_dwconv_desc* d0, const ydbl_dwconv_desc* d1, void* stream) {
-  if (!d0 || !d1) return fail(YDBL_EINVAL, "dw_pair: null descriptor");
-  if (d1->x.ptr != d0->y.ptr || d1->x.cs != d0->y.cs || d1->x.c != d0->y.c)
-    return fail(YDBL_EINVAL, "dw_pair: d1.x must be d0.y");
+// ydbl_dwconv2d_pair_nhwc's dispatch (include/ydbl.h ydbl_dwconv2d_pair_route): the two launches, dw_pair_kernel,
+// or dw_pair.hip's kernel
+constexpr int DWP_CV = 2;  // 16 (f16) / 8 (f32) channels per workgroup (CV = 1: 42 vs 38 us)
+static int dw_pair_route(const ydbl_dwconv_desc* d0, const ydbl_dwconv_desc* d1) {
   const bool pair = d0->kh == 5 && d0->kw == 5 && d0->dil == 1 && d1->kh == 7 && d1->kw == 7 && d1->dil == 3 &&
                     d0->stride == 1 && d1->stride == 1 && d0->res_mode == YDBL_RES_NONE &&
                     d1->res_mode == YDBL_RES_NONE && d0->x.h == d0->y.h && d0->x.w == d0->y.w &&
@@ -603,14 +607,32 @@ extern "C" int ydbl_dwconv2d_pair_nhwc(const ydbl_dwconv_desc* d0, const ydbl_dw
                     d0->x.dtype == d0->y.dtype && d1->y.dtype == d0->y.dtype && d0->x.c == d0->y.c &&
                     d1->y.c == d0->y.c && d0->x.n == d0->y.n && d1->y.n == d0->y.n;
   const int V = d0->x.dtype == YDBL_F16 ? 8 : 4;
-  constexpr int CV = 2;  // 16 (f16) / 8 (f32) channels per workgroup (CV = 1: 42 vs 38 us)
-  if (!pair || d0->y.c % (CV * V) || !d0->w || !d1->w || check_view(&d0->x, "dw_pair.x", true) ||
-      check_view(&d0->y, "dw_pair.y0", true) || check_view(&d1->y, "dw_pair.y1", true)) {
+  if (!pair || d0->y.c % (DWP_CV * V) || !d0->w || !d1->w || check_view(&d0->x, "dw_pair.x", true) ||
+      check_view(&d0->y, "dw_pair.y0", true) || check_view(&d1->y, "dw_pair.y1", true))
+    return 0;
+  return dw_pair_fast_ok(d0, d1) ? 2 : 1;
+}
+
+extern "C" int ydbl_dwconv2d_pair_route(const ydbl_dwconv_desc* d0, const ydbl_dwconv_desc* d1) {
+  if (!d0 || !d1) return -1;
+  return dw_pair_route(d0, d1);
+}
+
+extern "C" int ydbl_dwconv2d_pair_nhwc(const ydbl_dwconv_desc* d0, const ydbl_dwconv_desc* d1, void* stream) {
+  if (!d0 || !d1) return fail(YDBL_EINVAL, "dw_pair: null descriptor");
+  if (d1->x.ptr != d0->y.ptr || d1->x.cs != d0->y.cs || d1->x.c != d0->y.c)
+    return fail(YDBL_EINVAL, "dw_pair: d1.x must be d0.y");
+  const int route = dw_pair_route(d0, d1);
+  if (route == 0) {
     // not the fused geometry: the two launches
     const int r = ydbl_dwconv2d_nhwc(d0, stream);
     return r ? r : ydbl_dwconv2d_nhwc(d1, stream);
   }
   hipStream_t s = as_stream(stream);
+  // fp16, no activation, pads 2 / 9, both padded maps in half a CU's LDS (YDBL_DW_PAIR_OLD=1: never)
+  if (route == 2) return dw_pair_fast_launch(d0, d1, s);
+  constexpr int CV = DWP_CV;
+  const int V = d0->x.dtype == YDBL_F16 ? 8 : 4;
   const unsigned blocks = (unsigned)(d0->y.n * (d0->y.c / (CV * V)));
   constexpr int NT = 1024;
   if (d0->x.dtype == YDBL_F16)

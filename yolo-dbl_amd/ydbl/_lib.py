@@ -215,6 +215,7 @@ SIGNATURES = {
     "ydbl_conv2d_nhwc": ([C.POINTER(ConvDesc), _P], C.c_int),
     "ydbl_dwconv2d_nhwc": ([C.POINTER(DwConvDesc), _P], C.c_int),
     "ydbl_dwconv2d_pair_nhwc": ([C.POINTER(DwConvDesc), C.POINTER(DwConvDesc), _P], C.c_int),
+    "ydbl_dwconv2d_pair_route": ([C.POINTER(DwConvDesc), C.POINTER(DwConvDesc)], C.c_int),
     "ydbl_dsconv_nhwc": ([C.POINTER(DsConvDesc), _P], C.c_int),
     "ydbl_batch_max_work_ints": ([], C.c_int32),
     "ydbl_batch_max_work_init": ([_P], None),

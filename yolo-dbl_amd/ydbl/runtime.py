@@ -28,7 +28,7 @@ from ._lib import View, lib
 SWITCHES = ("YDBL_DS2_OFF", "YDBL_DS_LEAN", "YDBL_HG_UNFUSED", "YDBL_HALO_NB", "YDBL_HALO_SMALL", "YDBL_VW", "YDBL_WSK_HALF",
             "YDBL_LSK_FUSE", "YDBL_NMS_FAST", "YDBL_NMS_GROUPS", "YDBL_SPLITK", "YDBL_NO_BNECK", "YDBL_NO_BOX3",
             "YDBL_NO_CLS_TAIL", "YDBL_DWPW", "YDBL_NO_PAIR3", "YDBL_NO_FUSE_PAD", "YDBL_NO_MERGE", "YDBL_NO_STEM2",
-            "YDBL_EPI_GENERIC", "YDBL_NO_SPARSE_BOX", "YDBL_NO_HG_PAIR")
+            "YDBL_EPI_GENERIC", "YDBL_NO_SPARSE_BOX", "YDBL_NO_HG_PAIR", "YDBL_DW_PAIR_OLD")
 
 
 def ydbl_env() -> tuple:
