@@ -38,6 +38,9 @@
  *   ydbl_gate_add          <- FullPAD_Tunnel.forward nn/modules/block.py:1954-1956
  *   ydbl_channel_gate_add  <- A2C2f.forward block.py:1404-1405 (x + gamma * y)
  *   ydbl_area_attn         <- AAttn.forward block.py:1243-1264 (softmax(q^T k / sqrt(32)) v per area chunk)
+ *   ydbl_psa_attn          <- Attention.forward block.py:919-928 (C2PSA / PSABlock: softmax(q^T k / sqrt(32)) v over
+ *                             all tokens, key_dim 32, head_dim 64) without its convs
+ *   ydbl_maxpool5_cascade  <- SPPF.forward block.py:194-198 (the three chained MaxPool2d(5, 1, 2))
  *   ydbl_pool_up_concat    <- FuseModule.forward block.py:1831-1840, DownsampleConv block.py:1927,
  *                             nn.Upsample(scale_factor=2, mode="nearest")
  *   ydbl_dysample(_ex)     <- DySample.sample modules_upsample/DySample.py:48-61 (grid_sample border)
@@ -279,6 +282,35 @@ typedef struct {
   float scale;
 } ydbl_area_attn_desc;
 int ydbl_area_attn(const ydbl_area_attn_desc* d, void* stream);
+
+/* C2PSA's attention core (Attention.forward without its convs, U/nn/modules/block.py:919-928), key_dim 32, head_dim 64.
+ * qkv: [n,h,w,heads*128] NHWC view, channel = head*128 + {q 0..31 | k 32..63 | v 64..127} (the reference's
+ * view(B, heads, 2*kd + hd, N).split -- not q | k | v by thirds).  For each (image, head): P = softmax(q k^T * scale)
+ * over all N = h*w keys (scale = key_dim^-0.5 in the reference), y = P v.
+ * y: [n,h,w,heads*64] view, channel = head*64 + d.  v: the V part re-laid the same way (the input of Attention.pe),
+ * or a null view (ptr NULL) to skip it.  Any N >= 1: key / value tiles stream through LDS with an online softmax, tail
+ * keys masked.  f16: f16 MFMA, fp32 maximum, sum and accumulators, P rounded to f16 for P v; f32: the fp32 MFMA.
+ * All views 16-byte aligned channel vectors; y and v must not overlap qkv or each other.  key_dim and head_dim are
+ * descriptor fields so that a caller states what it has: anything but 32 / 64 is YDBL_EINVAL.
+ * Grid (query tile of 64, head, image): heads <= 65535, n <= 65535, h*w < 2^31, else YDBL_EINVAL. */
+typedef struct {
+  ydbl_view qkv, y, v;
+  int32_t heads, key_dim, head_dim;
+  float scale;
+} ydbl_psa_attn_desc;
+int ydbl_psa_attn(const ydbl_psa_attn_desc* d, void* stream);
+
+/* SPPF's three cascaded max-pools (U/nn/modules/block.py:179-198) in one launch: y1 = m(x), y2 = m(y1), y3 = m(y2),
+ * m = MaxPool2d(k, 1, k / 2) with -inf padding, computed as the 5x5, 9x9 and 13x13 windowed maxima of x clipped at the
+ * border -- the same values exactly (a maximum never rounds; NaN propagates as in torch; the sign of a zero that ties
+ * with the other zero is unspecified).  x, y1, y2, y3: [n,h,w,c] views of one shape and dtype, typically four channel
+ * slices of SPPF's concat buffer (cs >= c), 16-byte aligned channel vectors; no output may overlap x or another
+ * output.  k must be 5.  n <= 65535, c <= 131070 channel vectors, n*h < 2^31, else YDBL_EINVAL. */
+typedef struct {
+  ydbl_view x, y1, y2, y3;
+  int32_t k;
+} ydbl_maxpool5_desc;
+int ydbl_maxpool5_cascade(const ydbl_maxpool5_desc* d, void* stream);
 
 /* y[..., off0:] = avgpool2(p_lo); y[..., off1:] = p_mid; y[..., off2:] = nearest_up2(p_hi).
  * Any of p_lo / p_mid / p_hi may be NULL (DownsampleConv uses p_lo only). */

@@ -310,4 +310,18 @@ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 int check_view(const ydbl_view* v, const char* name, bool need_vec_align);
 
+// Do two checked views share an element?  Views whose byte extents intersect count as overlapping unless they are
+// channel slices of one buffer (same channel stride and dtype) with disjoint channel ranges.
+inline bool views_overlap(const ydbl_view& a, const ydbl_view& b) {
+  const int64_t esa = a.dtype == YDBL_F16 ? 2 : 4, esb = b.dtype == YDBL_F16 ? 2 : 4;
+  const auto pa = reinterpret_cast<uintptr_t>(a.ptr), pb = reinterpret_cast<uintptr_t>(b.ptr);
+  const uintptr_t ea = pa + (((int64_t)a.n * a.h * a.w - 1) * a.cs + a.c) * esa;
+  const uintptr_t eb = pb + (((int64_t)b.n * b.h * b.w - 1) * b.cs + b.c) * esb;
+  if (ea <= pb || eb <= pa) return false;
+  if (a.cs != b.cs || a.dtype != b.dtype) return true;
+  const int64_t row = (int64_t)a.cs * esa;
+  const int64_t r = pb >= pa ? int64_t((pb - pa) % row) : int64_t((row - int64_t((pa - pb) % row)) % row);
+  return !(r >= a.c * esa && r + b.c * esb <= row);  // b's channels start r bytes after a's within a pixel
+}
+
 }  // namespace ydbl

@@ -171,6 +171,17 @@ class AreaAttnDesc(C.Structure):
                 ("scale", C.c_float)]
 
 
+class PsaAttnDesc(C.Structure):
+    """ydbl_psa_attn_desc: C2PSA's attention core, 128 channels per head (q 32 | k 32 | v 64)."""
+    _fields_ = [("qkv", View), ("y", View), ("v", View), ("heads", C.c_int32), ("key_dim", C.c_int32),
+                ("head_dim", C.c_int32), ("scale", C.c_float)]
+
+
+class MaxPool5Desc(C.Structure):
+    """ydbl_maxpool5_desc: SPPF's three cascaded MaxPool2d(5, 1, 2), one launch."""
+    _fields_ = [("x", View), ("y1", View), ("y2", View), ("y3", View), ("k", C.c_int32)]
+
+
 class AvgPoolDesc(C.Structure):
     """ydbl_avgpool_desc: global average pool of an NHWC view into rows of a [B, D] buffer (Model.embed)."""
     _fields_ = [("x", View), ("y", C.c_void_p), ("y_stride", C.c_int64), ("workspace", C.c_void_p),
@@ -228,6 +239,8 @@ SIGNATURES = {
     "ydbl_gate_add": ([_VP, _VP, C.c_float, _VP, _P], C.c_int),
     "ydbl_channel_gate_add": ([_VP, _VP, _P, _VP, _P], C.c_int),
     "ydbl_area_attn": ([C.POINTER(AreaAttnDesc), _P], C.c_int),
+    "ydbl_psa_attn": ([C.POINTER(PsaAttnDesc), _P], C.c_int),
+    "ydbl_maxpool5_cascade": ([C.POINTER(MaxPool5Desc), _P], C.c_int),
     "ydbl_pool_up_concat": ([_VP, _VP, _VP, _VP, _P], C.c_int),
     "ydbl_dysample": ([_VP, _VP, C.c_int32, _VP, _P], C.c_int),
     "ydbl_dysample_ex": ([C.POINTER(DySampleDesc), _P], C.c_int),

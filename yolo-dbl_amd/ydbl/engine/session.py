@@ -231,6 +231,11 @@ class DetectSession(BatchSession):
         if opt.fp8 and any(type(m).__name__ == "A2C2f" for m in model.modules()):
             raise NotImplementedError("fp8=True on a model with A2C2f: no calibration record exists for the "
                                       "area-attention blocks")
+        if opt.fp8:
+            for name in ("C2PSA", "SPPF"):
+                if any(type(m).__name__ == name for m in model.modules()):
+                    raise NotImplementedError(f"fp8=True on a model with {name}: no calibration record exists for "
+                                              "the YOLO11 / YOLOv8 baselines")
         # loss: ydbl_detect_loss behind the head (_emit_loss).  The loss normalises by the whole batch's target scores,
         # so the batch stays one plan, and it reads every level's box logits, so the levels stay dense (no sparse box
         # path)

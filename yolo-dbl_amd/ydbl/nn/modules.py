@@ -793,6 +793,118 @@ class DSC3k2(C2f):
             )
 
 
+class SPPF(PlanModule):
+    """U/nn/modules/block.py:179-198 — cv1 writes slice 0 of one [n,h,w,4c_] buffer, one ydbl_maxpool5_cascade launch
+    fills slices 1-3 (the three chained 5x5 max-pools), cv2 reads the buffer: no concat copy."""
+
+    def __init__(self, c1, c2, k=5):
+        super().__init__()
+        c_ = c1 // 2
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv(c_ * 4, c2, 1, 1)
+        self.m = nn.MaxPool2d(kernel_size=k, stride=1, padding=k // 2)
+
+    def emit(self, plan, x, out=None):
+        if self.m.kernel_size != 5:
+            raise NotImplementedError(f"SPPF: k={self.m.kernel_size}; the HIP pool cascade is built for 5")
+        c_ = self.cv1.conv.out_channels
+        buf = plan.alloc(x.n, x.h, x.w, 4 * c_)
+        self.cv1.emit(plan, x, buf.cslice(0, c_))
+        d = _lib.MaxPool5Desc(*[buf.cslice(i * c_, c_).struct() for i in range(4)], 5)
+        plan.launch("ydbl_maxpool5_cascade", d, what="SPPF.pool5x3", keep=[d])
+        return self.cv2.emit(plan, buf, out)
+
+
+class C3k(C3):
+    """U/nn/modules/block.py:745-753 — C3 with k x k Bottlenecks at e=1.0."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5, k=3):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*(Bottleneck(c_, c_, shortcut, g, k=(k, k), e=1.0) for _ in range(n)))
+
+
+class C3k2(C2f):
+    """U/nn/modules/block.py:734-742 — C2f whose blocks are C3k(c, c, 2) or the default Bottleneck (k=(3, 3), e=0.5,
+    unlike C2f's own); they chain through the slices of the concat buffer (C2f.emit)."""
+
+    def __init__(self, c1, c2, n=1, c3k=False, e=0.5, g=1, shortcut=True):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.m = nn.ModuleList(
+            C3k(self.c, self.c, 2, shortcut, g) if c3k else Bottleneck(self.c, self.c, shortcut, g) for _ in range(n))
+
+
+class Attention(PlanModule):
+    """U/nn/modules/block.py:896-930 — qkv 1x1 -> softmax(q^T k / sqrt(key_dim)) v over all tokens (ydbl_psa_attn)
+    -> + pe(v) (3x3 depthwise, the add in its epilogue) -> proj 1x1."""
+
+    def __init__(self, dim, num_heads=8, attn_ratio=0.5):
+        super().__init__()
+        self.num_heads = num_heads
+        self.head_dim = dim // num_heads
+        self.key_dim = int(self.head_dim * attn_ratio)
+        self.scale = self.key_dim**-0.5
+        nh_kd = self.key_dim * num_heads
+        h = dim + nh_kd * 2
+        self.qkv = Conv(dim, h, 1, act=False)
+        self.proj = Conv(dim, dim, 1, act=False)
+        self.pe = Conv(dim, dim, 3, 1, g=dim, act=False)
+
+    def emit(self, plan, x, out=None, res=None):
+        """res: a view added to the result in proj's epilogue (PSABlock's x + attn(x))."""
+        if self.head_dim != 64 or self.key_dim != 32:
+            raise NotImplementedError(f"Attention: head_dim {self.head_dim}, key_dim {self.key_dim}; the HIP kernel "
+                                      "is built for 64 / 32 (C2PSA's)")
+        c = self.num_heads * self.head_dim
+        qkv = self.qkv.emit(plan, x)
+        att, v = plan.alloc(x.n, x.h, x.w, c), plan.alloc(x.n, x.h, x.w, c)
+        d = _lib.PsaAttnDesc(qkv.struct(), att.struct(), v.struct(), self.num_heads, self.key_dim, self.head_dim,
+                             self.scale)
+        plan.launch("ydbl_psa_attn", d, what="PSA.attn", keep=[d])
+        t = self.pe.emit(plan, v, None, res=att, res_mode=_lib.RES_ADD)  # attention + pe(v)
+        return self.proj.emit(plan, t, out, res=res, res_mode=_lib.RES_ADD if res is not None else _lib.RES_NONE)
+
+
+class PSABlock(PlanModule):
+    """U/nn/modules/block.py:955-967 — x + attn(x), then x + ffn(x); both adds ride in conv epilogues."""
+
+    def __init__(self, c, attn_ratio=0.5, num_heads=4, shortcut=True):
+        super().__init__()
+        self.attn = Attention(c, attn_ratio=attn_ratio, num_heads=num_heads)
+        self.ffn = nn.Sequential(Conv(c, c * 2, 1), Conv(c * 2, c, 1, act=False))
+        self.add = shortcut
+
+    def emit(self, plan, x, out=None):
+        """out may be x itself (C2PSA's last block): the launches that read x (qkv, proj's residual) precede
+        ffn[1], which reads only buffers of this block."""
+        x1 = self.attn.emit(plan, x, None, res=x if self.add else None)
+        h = self.ffn[0].emit(plan, x1)
+        return self.ffn[1].emit(plan, h, out, res=x1 if self.add else None,
+                                res_mode=_lib.RES_ADD if self.add else _lib.RES_NONE)
+
+
+class C2PSA(PlanModule):
+    """U/nn/modules/block.py:1038-1052 — cv1 writes [a | b] into one 2c buffer, the n PSABlocks run b -> b', the last
+    one back into the b slice, cv2 reads the buffer."""
+
+    def __init__(self, c1, c2, n=1, e=0.5):
+        super().__init__()
+        assert c1 == c2
+        self.c = int(c1 * e)
+        self.cv1 = Conv(c1, 2 * self.c, 1, 1)
+        self.cv2 = Conv(2 * self.c, c1, 1)
+        self.m = nn.Sequential(*(PSABlock(self.c, attn_ratio=0.5, num_heads=self.c // 64) for _ in range(n)))
+
+    def emit(self, plan, x, out=None):
+        c, n = self.c, len(self.m)
+        buf = plan.alloc(x.n, x.h, x.w, 2 * c)
+        self.cv1.emit(plan, x, buf)
+        b = buf.cslice(c, c)
+        for i, m in enumerate(self.m):  # intermediate b's get buffers of their own
+            b = m.emit(plan, b, buf.cslice(c, c) if i == n - 1 else None)
+        return self.cv2.emit(plan, buf, out)
+
+
 class AAttn(PlanModule):
     """U/nn/modules/block.py:1187-1264 — area attention: qkv 1x1 -> softmax(q^T k / sqrt(d)) v inside each of the
     `area` contiguous token chunks (ydbl_area_attn) -> + pe(v) (7x7 depthwise) -> proj 1x1."""

@@ -37,12 +37,13 @@ REGISTRY: dict[str, type] = {
     c.__name__: c
     for c in (M.Conv, M.DWConv, M.DSConv, M.GhostConv, M.Concat, M.Bottleneck, M.C2f, M.C3, M.C3Ghost,
               M.GhostBottleneck, M.DSBottleneck, M.DSC3k, M.DSC3k2, M.HyperACE, M.DownsampleConv,
-              M.FullPAD_Tunnel, M.DySample, M.LSKblock, M.Detect, M.AAttn, M.ABlock, M.A2C2f)
+              M.FullPAD_Tunnel, M.DySample, M.LSKblock, M.Detect, M.AAttn, M.ABlock, M.A2C2f, M.SPPF, M.C3k, M.C3k2,
+              M.Attention, M.PSABlock, M.C2PSA)
 }
 REGISTRY["nn.Upsample"] = M.Upsample  # the one torch.nn layer name the v13 YAMLs use (U/nn/tasks.py:972-973)
 _C1C2 = {"Conv", "DWConv", "GhostConv", "Bottleneck", "GhostBottleneck", "C2f", "C3", "C3Ghost", "DSC3k2", "DSConv",
-         "DSBottleneck", "A2C2f"}
-_REPEAT_ARG = {"C2f", "C3", "C3Ghost", "DSC3k2", "A2C2f"}
+         "DSBottleneck", "A2C2f", "SPPF", "C3k2", "C2PSA"}
+_REPEAT_ARG = {"C2f", "C3", "C3Ghost", "DSC3k2", "A2C2f", "C3k2", "C2PSA"}
 _C1_ONLY = {"DySample", "LSKblock"}
 
 
@@ -160,7 +161,7 @@ def parse_model(d: dict, ch: int = 3, verbose: bool = False):
             if name in _REPEAT_ARG:
                 args.insert(2, n)
                 n = 1
-            if name == "DSC3k2":
+            if name in ("DSC3k2", "C3k2"):  # U/nn/tasks.py:1084-1085
                 legacy = False
             if name == "A2C2f":  # U/nn/tasks.py:1087-1091
                 legacy = False
@@ -195,6 +196,7 @@ def parse_model(d: dict, ch: int = 3, verbose: bool = False):
         if name == "Detect":
             m.legacy = legacy  # class attribute, as the reference sets it (U/nn/tasks.py:1111-1112)
             m_ = m(*args)
+            m_.legacy = legacy  # and on the instance: a yolov8 (legacy) and a yolo11 model may live in one process
         else:
             m_ = nn.Sequential(*(m(*args) for _ in range(n))) if n > 1 else m(*args)
         m_.np = sum(x.numel() for x in m_.parameters())
@@ -545,13 +547,13 @@ def _propagate_shapes(layers, batch, h, w, ch):
         elif t in ("Bottleneck", "DSBottleneck"):
             cur = (batch, src[1], src[2], (m[-1] if isinstance(m, nn.Sequential) else m).cv2.conv.out_channels
                    if t == "Bottleneck" else (m[-1] if isinstance(m, nn.Sequential) else m).cv2.pw.out_channels)
-        elif t in ("C2f", "DSC3k2", "A2C2f"):
+        elif t in ("C2f", "DSC3k2", "A2C2f", "C3k2", "SPPF", "C2PSA"):
             cur = (batch, src[1], src[2], mm.cv2.conv.out_channels)
-        elif t in ("AAttn", "ABlock"):
+        elif t in ("AAttn", "ABlock", "Attention", "PSABlock"):
             cur = src
         elif t == "nn.Upsample":
             cur = (batch, 2 * src[1], 2 * src[2], src[3])
-        elif t in ("C3", "C3Ghost"):
+        elif t in ("C3", "C3Ghost", "C3k"):
             cur = (batch, src[1], src[2], mm.cv3.conv.out_channels)
         elif t == "LSKblock":
             cur = src
