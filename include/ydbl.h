@@ -133,7 +133,32 @@ typedef struct {
   int64_t workspace_bytes;
 } ydbl_conv_desc;
 int ydbl_conv2d_nhwc(const ydbl_conv_desc* d, void* stream);
+/* ydbl_conv_workspace: the split-K scratch, in bytes, of the route this descriptor takes when it has all the room it
+ * asks for (the environment switches as they are now); 0: that route does not split; -1: an invalid descriptor.
+ * ydbl_conv_route: what ydbl_conv2d_nhwc would launch for this descriptor (its workspace as given, the switches as
+ * they are now), without launching; YDBL_OK, or YDBL_EINVAL for an invalid descriptor or a NULL out.
+ *   family  v[0..3]
+ *   VW      Cin of the instance (128 or 64), output rows per tile        VGPR-weight 3x3 (conv3x3_vw_kernel)
+ *   TILE    Cin, 16-channel output tiles, stride                         thin-input spatial tile (conv3x3_tile_kernel)
+ *   HALO    stride, images per workgroup, channel-slice width (32 / 64)  halo 3x3 (conv3x3_halo_kernel)
+ *   WSK     BM, BN                                                       wave-split-K (conv_wsk_kernel)
+ *   IGEMM   BM, BN, WM, WN                                               block implicit GEMM (conv_igemm_kernel)
+ * pointwise: the 1x1 / stride 1 / pad 0 instance.  ksplit > 1: a split-K launch followed by the epilogue kernel.
+ * epi: the epilogue form compiled into the chosen instance, YDBL_ACT_SILU or YDBL_ACT_NONE; -1: the form that reads
+ * the descriptor at run time; -2: the kernel picks the form itself, once per wave.  grid: the (first) kernel's grid.
+ * workspace_bytes: ydbl_conv_workspace(d), whatever workspace the descriptor carries. */
+enum { YDBL_CONV_VW = 0, YDBL_CONV_TILE = 1, YDBL_CONV_HALO = 2, YDBL_CONV_WSK = 3, YDBL_CONV_IGEMM = 4 };
+typedef struct {
+  int32_t family;
+  int32_t v[4];
+  int32_t pointwise;
+  int32_t ksplit;
+  int32_t epi;
+  uint32_t grid[3];
+  int64_t workspace_bytes;
+} ydbl_conv_route_info;
 int64_t ydbl_conv_workspace(const ydbl_conv_desc* d);
+int ydbl_conv_route(const ydbl_conv_desc* d, ydbl_conv_route_info* out);
 
 /* DSConv in one kernel (conv.py:91-108): y = act(pw(dw(x)) + bias) [+ r], BN folded into pw.
  * dw_w fp32 [k*k][cin], pw_w [cout][kpad] in the view dtype (kpad = round_up(cin, 32), zero

@@ -34,6 +34,7 @@ def test_library_exports_every_declared_symbol():
 STRUCTS = {
     "ydbl_view": "View",
     "ydbl_conv_desc": "ConvDesc",
+    "ydbl_conv_route_info": "ConvRouteInfo",
     "ydbl_dwconv_desc": "DwConvDesc",
     "ydbl_dsconv_desc": "DsConvDesc",
     "ydbl_hg_desc": "HgDesc",

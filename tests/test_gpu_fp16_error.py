@@ -184,8 +184,10 @@ def _check(name, got, ref, stages, emu, variant):
 
 # ------------------------------------------------------------------------------------------- dense convs
 # name: (cin, cout, k, stride, act, residual, n, h, w, environment, options)
+# environment: a value of None unsets the switch
 # options: seeds (pool that many draws: the shape alone has < 4096 outputs), ws (the launch must get a split-K
-# workspace), second (the fused FullPAD second output)
+# workspace), second (the fused FullPAD second output), route (the kernel family ydbl_conv_route must report under the
+# case's environment: the switch reaches the kernel the case is named for; with the halo kernel's images per workgroup)
 DENSE = {
     # block implicit GEMM and pointwise, the test_conv_dense shapes at 2 x 13 x 11
     "igemm-64-64-k3-add": (64, 64, 3, 1, "silu", "add", 2, 13, 11, {}, {}),
@@ -201,13 +203,13 @@ DENSE = {
     "splitk-512-64-k3": (512, 64, 3, 1, "silu", None, 2, 20, 20, {}, {"ws": True}),
     "halo-split-384-128": (384, 128, 3, 1, "silu", None, 2, 40, 40, {}, {"ws": True}),
     # the other 3x3 routes, each at the smallest case of its test in test_gpu_ops.py that has >= 4096 outputs
-    "halo-s1": (64, 32, 3, 1, "silu", None, 2, 161, 163, {"YDBL_HALO_NB": "1"}, {}),
+    "halo-s1": (64, 32, 3, 1, "silu", None, 2, 161, 163, {"YDBL_HALO_NB": "1"}, {"route": ("HALO", 1)}),
     "halo-s2": (64, 64, 3, 2, "silu", None, 8, 320, 320, {}, {}),
-    "halo-small-map": (64, 128, 3, 1, "silu", None, 3, 37, 41, {"YDBL_HALO_SMALL": "1"}, {}),
-    "halo-nblock": (64, 96, 3, 1, "silu", None, 17, 37, 45, {"YDBL_HALO_NB": "2", "YDBL_SPLITK": "0"}, {}),
+    "halo-small-map": (64, 128, 3, 1, "silu", None, 3, 37, 41, {"YDBL_HALO_SMALL": "1"}, {"route": ("HALO", 2)}),
+    "halo-nblock": (64, 96, 3, 1, "silu", None, 17, 37, 45, {"YDBL_HALO_NB": None, "YDBL_SPLITK": "0"}, {"route": ("HALO", 2)}),
     "tile-8-8": (8, 8, 3, 1, "silu", None, 2, 70, 66, {}, {}),
     "tile-16-32-s2-add": (16, 32, 3, 2, "silu", "add", 2, 131, 129, {}, {}),
-    "vw-128-64-add": (128, 64, 3, 1, "silu", "add", 3, 21, 19, {"YDBL_VW": "1"}, {}),
+    "vw-128-64-add": (128, 64, 3, 1, "silu", "add", 3, 21, 19, {"YDBL_VW": "1"}, {"route": ("VW", None)}),
 }
 # one shape per dense family for the value ranges (no residual there: the conv's own result is what is measured)
 DENSE_RANGE = ["igemm-64-64-k3-add", "pw-24-80", "wsk-512-96-k1-add", "splitk-512-64-k3", "tile-16-32-s2-add"]
@@ -257,6 +259,15 @@ def _dense_gpu(d, opts):
     desc = plan.steps[-1].args[0]
     if opts.get("ws"):
         assert desc.workspace and desc.workspace_bytes == _lib.lib.ydbl_conv_workspace(desc) > 0
+    if opts.get("route") or opts.get("ws"):
+        route = _lib.ConvRouteInfo()
+        _lib.check(_lib.lib.ydbl_conv_route(desc, route), "ydbl_conv_route")
+        if opts.get("ws"):
+            assert route.ksplit > 1, "the launch does not split"
+        else:
+            family, nb = opts["route"]
+            assert route.family == getattr(_lib, "CONV_" + family) and nb in (None, route.v[1]), (
+                route.family, list(route.v))
     y2 = None
     if opts.get("second"):
         y2 = _out(plan, n, ho, wo, co)
@@ -269,7 +280,10 @@ def _dense_case(name, variant, monkeypatch):
     case = DENSE[name]
     env, opts = case[9], case[10]
     for k, v in env.items():
-        monkeypatch.setenv(k, v)
+        if v is None:
+            monkeypatch.delenv(k, raising=False)
+        else:
+            monkeypatch.setenv(k, v)
     gots, refs, emus, seconds = [], [], [], []
     for i in range(opts.get("seeds", 1)):
         d = _dense_draw(case, 1000 * case[0] + case[1] + case[2] + 7919 * i, variant)

@@ -39,6 +39,16 @@ def _run(plan):
     torch.cuda.synchronize()
 
 
+def _conv_route(d):
+    """What ydbl_conv2d_nhwc launches for descriptor d under the switches as they are now (include/ydbl.h
+    ydbl_conv_route): (family, v, pointwise, ksplit, epi, grid)."""
+    from ydbl import _lib
+
+    r = _lib.ConvRouteInfo()
+    _lib.check(_lib.lib.ydbl_conv_route(d, r), "ydbl_conv_route")
+    return (r.family, tuple(r.v), r.pointwise, r.ksplit, r.epi, tuple(r.grid))
+
+
 def _tol(dtype):
     return dict(rtol=2e-5, atol=2e-5) if dtype == torch.float32 else dict(rtol=2e-2, atol=2e-2)
 
@@ -103,7 +113,7 @@ def test_conv_wsk_split_k(dtype, cin, cout, k, n, h, w, res):
     wt = torch.randn(cout, cin, k, k) / (cin * k * k) ** 0.5
     b = torch.randn(cout)
     ref = F.silu(F.conv2d(x.to(dtype).float(), wt.to(dtype).float(), b, 1, k // 2))
-    outs = []
+    outs, routes = [], []
     for split in (True, False):
         plan = _plan(dtype)
         xv = _tv_from_nchw(plan, x, cs_extra=8, c_off=8)
@@ -119,12 +129,14 @@ def test_conv_wsk_split_k(dtype, cin, cout, k, n, h, w, res):
             assert d.workspace and d.workspace_bytes == _lib.lib.ydbl_conv_workspace(d) > 0
         else:
             d.workspace, d.workspace_bytes = None, 0
+        routes.append(_conv_route(d))
         r2 = torch.randn(n, cout, h, w, generator=torch.Generator().manual_seed(6))
         r2v = _tv_from_nchw(plan, r2)
         y2 = plan.alloc(n, h, w, cout)
         assert plan.fuse_second_output(plan.writer_of(yv), y2, r2v, 0.5, 1.0) is not None
         _run(plan)
         outs.append((yv.nchw().float().cpu(), y2.nchw().float().cpu()))
+    assert routes[0][3] > 1 and routes[1][3] == 1, routes  # the two runs are the split and the unsplit launch
     want = ref
     if res:
         rr = r.to(dtype).float()
@@ -137,9 +149,9 @@ def test_conv_wsk_split_k(dtype, cin, cout, k, n, h, w, res):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
 @pytest.mark.parametrize("cin,cout,n,h,w", [(384, 64, 16, 40, 40), (256, 32, 4, 80, 80), (64, 96, 17, 37, 45)])
 def test_conv3x3_halo_nblock(monkeypatch, dtype, cin, cout, n, h, w):
-    """The halo 3x3 kernel with two images per workgroup (YDBL_HALO_NB=2: every staged weight chunk feeds both
+    """The halo 3x3 kernel with two images per workgroup (the default: every staged weight chunk feeds both
     images' tiles; odd batches leave the last block's second image masked) vs F.conv2d fp32, and equal to the one-image
-    workgroups (the same per-output k order)."""
+    workgroups (YDBL_HALO_NB=1; the same per-output k order)."""
     from ydbl import _lib
     from ydbl.nn.modules import emit_dense
 
@@ -148,16 +160,22 @@ def test_conv3x3_halo_nblock(monkeypatch, dtype, cin, cout, n, h, w):
     wt = torch.randn(cout, cin, 3, 3) / (cin * 9) ** 0.5
     b = torch.randn(cout)
     ref = F.silu(F.conv2d(x.to(dtype).float(), wt.to(dtype).float(), b, 1, 1))
-    outs = []
-    for nb in ("2", "1"):
-        monkeypatch.setenv("YDBL_HALO_NB", nb)
+    outs, routes = [], []
+    for nb in (None, "1"):
+        if nb is None:
+            monkeypatch.delenv("YDBL_HALO_NB", raising=False)
+        else:
+            monkeypatch.setenv("YDBL_HALO_NB", nb)
         monkeypatch.setenv("YDBL_SPLITK", "0")
         plan = _plan(dtype)
         xv = _tv_from_nchw(plan, x, cs_extra=8, c_off=8)
         yv = plan.alloc(n, h, w, cout + 8).cslice(4, cout)
         emit_dense(plan, xv, yv, wt, b, 1, 1, 1, _lib.ACT_SILU)
+        routes.append(_conv_route(plan.steps[-1].args[0]))
         _run(plan)
         outs.append(yv.nchw().float().cpu())
+    # the halo kernel both times, two images per workgroup, then one
+    assert [(r[0], r[1][1]) for r in routes] == [(_lib.CONV_HALO, 2), (_lib.CONV_HALO, 1)], routes
     torch.testing.assert_close(outs[0], ref, **_tol(dtype))
     assert torch.equal(outs[0], outs[1]), (outs[0] - outs[1]).abs().max()
 
@@ -170,7 +188,7 @@ def test_conv3x3_halo_nblock(monkeypatch, dtype, cin, cout, n, h, w):
 ])
 def test_conv3x3_halo_small_map(monkeypatch, dtype, cin, cout, n, h, w, res):
     """Small maps (4096..25599 output pixels) with too few input-channel chunks to split and Cout >= 128 take the
-    halo tile instead of the wave-split-K kernel (conv3x3.hip try_conv3x3_halo): vs F.conv2d fp32, and against
+    halo tile instead of the wave-split-K kernel (conv_route.hpp route_halo): vs F.conv2d fp32, and against
     the wave-split-K route (YDBL_HALO_SMALL=0) to summation-order rounding."""
     from ydbl import _lib
     from ydbl.nn.modules import emit_dense
@@ -184,7 +202,7 @@ def test_conv3x3_halo_small_map(monkeypatch, dtype, cin, cout, n, h, w, res):
     if res:
         rr = r.to(dtype).float()
         ref = rr + ref if res == "add" else rr * ref
-    outs = []
+    outs, routes = [], []
     for route in ("1", "0"):
         monkeypatch.setenv("YDBL_HALO_SMALL", route)
         plan = _plan(dtype)
@@ -193,8 +211,10 @@ def test_conv3x3_halo_small_map(monkeypatch, dtype, cin, cout, n, h, w, res):
         rv = _tv_from_nchw(plan, r) if res else None
         mode = {None: _lib.RES_NONE, "add": _lib.RES_ADD, "mul": _lib.RES_MUL}[res]
         emit_dense(plan, xv, yv, wt, b, 1, 1, 1, _lib.ACT_SILU, rv, mode)
+        routes.append(_conv_route(plan.steps[-1].args[0]))
         _run(plan)
         outs.append(yv.nchw().float().cpu())
+    assert routes[0][0] == _lib.CONV_HALO and routes[1][0] != _lib.CONV_HALO, routes  # the switch moved the route
     torch.testing.assert_close(outs[0], ref, **_tol(dtype))
     torch.testing.assert_close(outs[1], ref, **_tol(dtype))
     tol = dict(rtol=1e-5, atol=1e-5) if dtype == torch.float32 else dict(rtol=1e-2, atol=1e-2)
@@ -318,6 +338,8 @@ def test_conv3x3_halo(dtype, n, cin, cout, h, w, res, monkeypatch):
         mode = _lib.RES_ADD
         ref = r.to(dtype).float() + ref
     emit_dense(plan, xv, yv, wt, b, 1, 1, 1, _lib.ACT_SILU, rv, mode)
+    route = _conv_route(plan.steps[-1].args[0])
+    assert route[0] == _lib.CONV_HALO and route[1][:2] == (1, 1), route  # stride 1, one image per workgroup
     _run(plan)
     tol = _tol(dtype) if dtype == torch.float32 else dict(rtol=3e-2, atol=3e-2)
     torch.testing.assert_close(yv.nchw().float().cpu(), ref, **tol)
@@ -389,7 +411,11 @@ def test_conv3x3_vw(n, cin, cout, h, w, res, monkeypatch):
         mode = _lib.RES_ADD
         ref = r.to(dtype).float() + ref
     emit_dense(plan, xv, yv, wt, b, 1, 1, 1, _lib.ACT_SILU, rv, mode)
+    route = _conv_route(plan.steps[-1].args[0])
     _run(plan)
+    monkeypatch.delenv("YDBL_VW")
+    off = _conv_route(plan.steps[-1].args[0])
+    assert route[0] == _lib.CONV_VW and off[0] != _lib.CONV_VW, (route, off)  # the switch moved the route
     torch.testing.assert_close(yv.nchw().float().cpu(), ref, **_tol(dtype))
     # the channels either side of the slice are untouched
     full = ybuf.torch().float().cpu()

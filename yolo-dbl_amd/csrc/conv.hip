@@ -9,9 +9,10 @@
 // f32 -> four exact-f32 v_mfma_f32_16x16x4_f32 (parity mode; same fmaf-chain numerics as VALU).
 // Fused epilogue: + bias, activation (SiLU/GELU/sigmoid), residual add or multiply, write into a
 // channel slice of a wider buffer (concat without copies).
+#include <stdint.h>
 #include <stdlib.h>
 
-#include "conv_common.hpp"
+#include "conv_route.hpp"
 
 namespace ydbl {
 
@@ -318,49 +319,32 @@ __global__ __launch_bounds__(256) void conv3x3_tile_kernel(ConvArgs<T> p, int ti
   conv_epilogue<T, NTN, TM, false, KA>(p, acc, pp, pv, co, s_bias, 0);
 }
 
+// The launchers below run the instance a ConvRoute names (conv_route.hpp); none of them chooses anything.
 template <typename T, int CIN, int S, int TH, int TW, int NTN>
-static void launch_tile(const ConvArgs<T>& a, hipStream_t s) {
+static void launch_tile(const ConvRoute& r, const ConvArgs<T>& a, hipStream_t s) {
   const int tiles_x = (int)cdiv(a.Wo, TW), tiles_y = (int)cdiv(a.Ho, TH);
-  const unsigned grid = (unsigned)(a.N * tiles_y * tiles_x);
   if constexpr (sizeof(T) == 2) {  // the epilogue form is part of the kernel (conv_common.hpp, conv_epilogue)
-    const int form = epi_host_form(a);
-    if (form == YDBL_ACT_SILU)
-      return conv3x3_tile_kernel<T, CIN, S, TH, TW, NTN, YDBL_ACT_SILU><<<grid, 256, 0, s>>>(a, tiles_x, tiles_y);
-    if (form == YDBL_ACT_NONE)
-      return conv3x3_tile_kernel<T, CIN, S, TH, TW, NTN, YDBL_ACT_NONE><<<grid, 256, 0, s>>>(a, tiles_x, tiles_y);
+    if (r.epi == YDBL_ACT_SILU)
+      return conv3x3_tile_kernel<T, CIN, S, TH, TW, NTN, YDBL_ACT_SILU><<<r.grid[0], 256, 0, s>>>(a, tiles_x, tiles_y);
+    if (r.epi == YDBL_ACT_NONE)
+      return conv3x3_tile_kernel<T, CIN, S, TH, TW, NTN, YDBL_ACT_NONE><<<r.grid[0], 256, 0, s>>>(a, tiles_x, tiles_y);
   }
-  conv3x3_tile_kernel<T, CIN, S, TH, TW, NTN, ACT_RT><<<grid, 256, 0, s>>>(a, tiles_x, tiles_y);
+  conv3x3_tile_kernel<T, CIN, S, TH, TW, NTN, ACT_RT><<<r.grid[0], 256, 0, s>>>(a, tiles_x, tiles_y);
 }
 
-// 3x3 / pad 1 / dil 1, Cin in {8,16,32}, Cout <= 64 and a multiple of 4: the spatial-tile kernel.
 template <typename T, int CIN, int NTN>
-static void launch_tile_s(const ConvArgs<T>& a, hipStream_t s) {
-  if (a.S == 1) launch_tile<T, CIN, 1, 8, 32, NTN>(a, s);
-  else launch_tile<T, CIN, 2, 8, 16, NTN>(a, s);
+static void launch_tile_s(const ConvRoute& r, const ConvArgs<T>& a, hipStream_t s) {
+  if (r.v[2] == 1) launch_tile<T, CIN, 1, 8, 32, NTN>(r, a, s);
+  else launch_tile<T, CIN, 2, 8, 16, NTN>(r, a, s);
 }
 
 template <typename T, int CIN>
-static bool tile_ntn(const ConvArgs<T>& a, hipStream_t s) {
-  switch ((a.Cout + 15) / 16) {
-    case 1: launch_tile_s<T, CIN, 1>(a, s); return true;
-    case 2: launch_tile_s<T, CIN, 2>(a, s); return true;
-    case 3: launch_tile_s<T, CIN, 3>(a, s); return true;
-    case 4: launch_tile_s<T, CIN, 4>(a, s); return true;
-    default: return false;
-  }
-}
-
-template <typename T>
-static bool try_tile(const ConvArgs<T>& a, int kh, hipStream_t s) {
-  if (kh != 3 || a.KW != 3 || a.DIL != 1 || a.PAD != 1 || a.Cout > 64 || a.Cout % 4) return false;
-  if (a.S != 1 && a.S != 2) return false;
-  if ((int64_t)a.Ho * a.Wo < 4096) return false;  // small maps: the GEMM kernel has more parallelism
-  if (a.xcs % Vec<T>::N) return false;
-  switch (a.Cin) {
-    case 8: return tile_ntn<T, 8>(a, s);
-    case 16: return tile_ntn<T, 16>(a, s);
-    case 32: return tile_ntn<T, 32>(a, s);
-    default: return false;
+static void launch_tile_ntn(const ConvRoute& r, const ConvArgs<T>& a, hipStream_t s) {
+  switch (r.v[1]) {
+    case 1: return launch_tile_s<T, CIN, 1>(r, a, s);
+    case 2: return launch_tile_s<T, CIN, 2>(r, a, s);
+    case 3: return launch_tile_s<T, CIN, 3>(r, a, s);
+    default: return launch_tile_s<T, CIN, 4>(r, a, s);
   }
 }
 
@@ -569,177 +553,103 @@ __global__ __launch_bounds__(256) void splitk_epilogue_kernel(ConvArgs<T> p) {
   conv_epilogue<T, 1, 1, Q8>(p, one, pp, pv, cc);
 }
 
-template <typename T, bool Q8>
-void launch_splitk_epilogue(const ConvArgs<T>& a, hipStream_t s) {
-  splitk_epilogue_kernel<T, Q8><<<(unsigned)cdiv((int64_t)a.P * ((a.Cout + 3) >> 2), 256), 256, 0, s>>>(a);
-}
-template void launch_splitk_epilogue<_Float16, false>(const ConvArgs<_Float16>&, hipStream_t);
-template void launch_splitk_epilogue<_Float16, true>(const ConvArgs<_Float16>&, hipStream_t);
-template void launch_splitk_epilogue<float, false>(const ConvArgs<float>&, hipStream_t);
-
-// Split of the wave-split-K k-loop for a BM x BN tiling: the serial k-block chain is what a deep-K conv on a small
-// map waits on (DBL-s bs4 sub-batch: 768->128 3x3 @40^2, 400 tiles of 54 k-block steps, about 1 us each: 53.7 us in
-// graph), so below 768 tiles (3 workgroups per CU) the loop is split over up to 4 workgroups, each keeping >= 8
-// steps.  YDBL_SPLITK=0 (read per launch): no split (A/B switch).
-constexpr int WSK_SPLIT_BELOW = 768;
-template <typename T>
-static int wsk_ksplit(const ConvArgs<T>& a, int bm, int bn) {
-  const char* e = getenv("YDBL_SPLITK");
-  if (sizeof(T) != 2 || (e && *e == '0')) return 1;  // fp16 only: the fp32 parity mode keeps one summation order
-  const int64_t tiles = cdiv(a.P, bm) * cdiv(a.Cout, bn);
-  const int nsteps = (int)cdiv(a.K, 16 * Vec<T>::N);  // BKB
-  if (tiles >= WSK_SPLIT_BELOW || nsteps < 16) return 1;
-  int k = (int)std::min<int64_t>(4, (WSK_SPLIT_BELOW + tiles - 1) / tiles);
-  while (k > 1 && nsteps / k < 8) --k;
-  return k;
-}
-template <typename T>
-static int64_t wsk_ws_bytes(const ConvArgs<T>& a, int ksplit) {
-  return ksplit > 1 ? (int64_t)ksplit * a.P * ((a.Cout + 3) & ~3) * 4 : 0;
-}
-
 // Two k-block steps in flight (kbench bs16: 256->64 3x3 @20^2 18.8 -> 17.4 us; three or four: no better)
 constexpr int WSK_PF = 2;
 
 template <typename T, bool Q8, int BM, int BN>
-static void launch_wsk(const ConvArgs<T>& a0, bool pointwise, hipStream_t s) {
-  ConvArgs<T> a = a0;
-  a.ksplit = wsk_ksplit(a, BM, BN);
-  if (a.ksplit > 1 && (!a.ws || a.ws_bytes < wsk_ws_bytes(a, a.ksplit))) a.ksplit = 1;  // no room: unsplit
-  dim3 grid((unsigned)cdiv(a.P, BM), (unsigned)cdiv(a.Cout, BN), (unsigned)a.ksplit);
-  if (a.ksplit > 1) {
-    if (pointwise) conv_wsk_kernel<T, BM, BN, true, Q8, WSK_PF, true><<<grid, 256, 0, s>>>(a);
+static void launch_wsk(const ConvRoute& r, const ConvArgs<T>& a, hipStream_t s) {
+  const dim3 grid(r.grid[0], r.grid[1], r.grid[2]);
+  if (r.ksplit > 1) {
+    if (r.pointwise) conv_wsk_kernel<T, BM, BN, true, Q8, WSK_PF, true><<<grid, 256, 0, s>>>(a);
     else conv_wsk_kernel<T, BM, BN, false, Q8, WSK_PF, true><<<grid, 256, 0, s>>>(a);
-    launch_splitk_epilogue<T, Q8>(a, s);
-  } else if (pointwise) {
+  } else if (r.pointwise) {
     conv_wsk_kernel<T, BM, BN, true, Q8, WSK_PF><<<grid, 256, 0, s>>>(a);
   } else {
     conv_wsk_kernel<T, BM, BN, false, Q8, WSK_PF><<<grid, 256, 0, s>>>(a);
   }
 }
 
-// The wave-split-K tiling try_wsk picks (BM, BN), without launching.
-template <typename T>
-static void wsk_tiles(const ConvArgs<T>& a, int& bm, int& bn) {
-  auto blocks = [&](int m, int n) { return cdiv(a.P, m) * cdiv(a.Cout, n); };
-  const int64_t want = 768;
-  const char* eh = getenv("YDBL_WSK_HALF");  // A/B switch (read per launch): 0 = no half-height tiles
-  if (a.Cout <= 128 && blocks(32, a.Cout <= 64 ? 64 : 128) < 256 && !(eh && *eh == '0')) {
-    bm = a.Cout <= 64 ? 16 : 32;
-    bn = 64;
-    return;
-  }
-  if (a.Cout <= 32) { bm = blocks(128, 32) >= want ? 128 : 64; bn = 32; return; }
-  if (a.Cout <= 64) { bm = blocks(64, 64) >= want ? 64 : 32; bn = 64; return; }
-  bm = 32;
-  bn = blocks(32, 128) >= want || a.Cout % 128 == 0 ? 128 : 64;
-}
-
-// Wave-split-K where the block-tiled GEMM runs out of parallelism or k-depth per barrier:
-// K >= 1024, or K >= 512 on small maps (measured on DBL-n: 384->64 3x3 @40^2 112 -> 82 us,
-// 256->64 3x3 @20^2 47 -> 27 us; 64->64 3x3 @80^2 stays on conv_igemm_kernel, 47 vs 74 us).
-template <typename T>
-static bool wsk_applies(const ConvArgs<T>& a) { return a.K >= 1024 || (a.K >= 512 && a.P <= 16384); }
-
-template <typename T, bool Q8>
-static bool try_wsk(const ConvArgs<T>& a, bool pointwise, hipStream_t s) {
-  if (!wsk_applies(a)) return false;
-  // Tiles (wsk_tiles): under 256 workgroups with the usual tiles (the 20^2 maps of a bs16 sub-batch): half-height
-  // tiles, 16 pixels for Cout <= 64 and 64-wide columns for Cout 128 -- twice the workgroups for the same k-loop
-  // (bs16 graphs: 128->128 3x3 s2 @20^2 17.4 -> 14.4 us, 64->64 3x3 @20^2 9.5 -> 8.6, 256->64 18.4 -> 17.7; DBL-n
-  // bs32 even to +0.5 % over two boxes, DBL-s bs64 even: profiles/r04/r04_wsk_small_tiles_ab.txt); then the
-  // k-loop split where the tiles are still few (wsk_ksplit)
-  int bm, bn;
-  wsk_tiles(a, bm, bn);
-  if (bm == 16) launch_wsk<T, Q8, 16, 64>(a, pointwise, s);
-  else if (bm == 32 && bn == 64) launch_wsk<T, Q8, 32, 64>(a, pointwise, s);
-  else if (bm == 32) launch_wsk<T, Q8, 32, 128>(a, pointwise, s);
-  else if (bm == 64 && bn == 64) launch_wsk<T, Q8, 64, 64>(a, pointwise, s);
-  else if (bm == 64) launch_wsk<T, Q8, 64, 32>(a, pointwise, s);
-  else launch_wsk<T, Q8, 128, 32>(a, pointwise, s);
-  return true;
-}
-
 // One k-step in flight: with the zero selects at the LDS store the loads of step s+1 overlap step s's MFMAs
 // (kbench bs16: 512->128 1x1 @40^2 16.9 -> 13.2 us, 128->64 @80^2 19.4 -> 11.1); deeper rings (2-4 steps,
 // the kernel's PF parameter) measured slower on every 1x1 shape (512->128: 13.4 / 14.6 / 14.2 us).
 template <typename T, bool Q8, int BM, int BN, int WM, int WN>
-static void launch_igemm(const ConvArgs<T>& a, bool pointwise, hipStream_t s) {
-  dim3 grid((unsigned)cdiv(a.P, BM), (unsigned)cdiv(a.Cout, BN));
-  // the epilogue form is part of the kernel (conv_common.hpp, conv_epilogue): fp16 SiLU / no activation compiled,
-  // for the 1x1 convs (the general form of the 128x64 and 64x64 tiles would lose a wave per SIMD to it)
-  if constexpr (sizeof(T) == 2 && !Q8) {
-    const int form = pointwise ? epi_host_form(a) : ACT_RT;
-    if (form == YDBL_ACT_SILU)
+static void launch_igemm(const ConvRoute& r, const ConvArgs<T>& a, hipStream_t s) {
+  const dim3 grid(r.grid[0], r.grid[1]);
+  if constexpr (sizeof(T) == 2 && !Q8) {  // the forms compiled for the 1x1 convs (route_igemm)
+    if (r.epi == YDBL_ACT_SILU)
       return conv_igemm_kernel<T, BM, BN, WM, WN, true, Q8, 1, YDBL_ACT_SILU><<<grid, 256, 0, s>>>(a);
-    if (form == YDBL_ACT_NONE)
+    if (r.epi == YDBL_ACT_NONE)
       return conv_igemm_kernel<T, BM, BN, WM, WN, true, Q8, 1, YDBL_ACT_NONE><<<grid, 256, 0, s>>>(a);
   }
-  if (pointwise)
+  if (r.pointwise)
     conv_igemm_kernel<T, BM, BN, WM, WN, true, Q8><<<grid, 256, 0, s>>>(a);
   else
     conv_igemm_kernel<T, BM, BN, WM, WN, false, Q8><<<grid, 256, 0, s>>>(a);
 }
 
 template <typename T, bool Q8>
-static void dispatch_conv(const ConvArgs<T>& a, bool pointwise, hipStream_t s) {
-  // BN covers Cout <= 64 in one column of workgroups (the input tile is then read once; wider Cout: below);
-  // BM is the largest pixel tile that still gives >= `want` workgroups: 512 (2 per CU) for small
-  // maps whose Cout fits one 128-wide column (bigger pixel tiles re-read the weights less:
-  // 512->128 1x1 @40^2 bs32 31.3 -> 23.0 us, 384->128 25.6 -> 19.4 us), 1024 otherwise
-  // (128->192: 16.4 vs 21.4 us; DBL-s bs64 end to end 0.8 % faster at 1024).
-  // Shallow K (<= 128) on large maps: 2048 (8 per CU; each tile is a short k-loop, so more workgroups
-  // hide each other's load latency: 64->128 @80^2 bs32 35.3 -> 28.1 us, 64->64 17.5 -> 16.4,
-  // 128->64 22.2 -> 21.2).
-  // (bs16 sub-batch graphs, scripts/kbench.py: for K 128, 2048 only above 131072 pixels -- 128->64 1x1 @80^2
-  // 12.6 -> 11.3 us at 1024; K 64 keeps 2048 there, 64->128 @80^2 14.4 vs 15.6 us -- and 64x64 tiles for the
-  // deep-K (>= 512) 3x3 convs with >= 16384 output pixels: 64->64 s2 @80^2 14.6 -> 13.1 us; DBL-n bs32 on two
-  // streams 16.20 -> 16.30 k img/s over three pairs with the halo kernel's n2_below 512, DBL-s bs64 even)
-  const int64_t want = a.Cout <= 128 && a.P <= 65536 ? 512
-                       : (a.K <= 128 && a.P > (a.K <= 64 ? 65536 : 131072) ? 2048 : 1024);
-  auto blocks = [&](int bm, int bn) { return cdiv(a.P, bm) * cdiv(a.Cout, bn); };
-  if (a.Cout <= 16) {
-    if (blocks(256, 16) >= want) return launch_igemm<T, Q8, 256, 16, 4, 1>(a, pointwise, s);
-    if (blocks(128, 16) >= want) return launch_igemm<T, Q8, 128, 16, 4, 1>(a, pointwise, s);
-    return launch_igemm<T, Q8, 64, 16, 4, 1>(a, pointwise, s);
+static void launch_as(const ConvRoute& r, const ConvArgs<T>& a, hipStream_t s) {
+  const int v0 = r.v[0], v1 = r.v[1];
+  switch (r.family) {
+    case YDBL_CONV_TILE:
+      if (v0 == 8) launch_tile_ntn<T, 8>(r, a, s);
+      else if (v0 == 16) launch_tile_ntn<T, 16>(r, a, s);
+      else launch_tile_ntn<T, 32>(r, a, s);
+      break;
+    case YDBL_CONV_WSK:
+      if (v0 == 16) launch_wsk<T, Q8, 16, 64>(r, a, s);
+      else if (v0 == 32 && v1 == 64) launch_wsk<T, Q8, 32, 64>(r, a, s);
+      else if (v0 == 32) launch_wsk<T, Q8, 32, 128>(r, a, s);
+      else if (v0 == 64 && v1 == 64) launch_wsk<T, Q8, 64, 64>(r, a, s);
+      else if (v0 == 64) launch_wsk<T, Q8, 64, 32>(r, a, s);
+      else launch_wsk<T, Q8, 128, 32>(r, a, s);
+      break;
+    case YDBL_CONV_IGEMM:
+      if (v1 == 16) {
+        if (v0 == 256) launch_igemm<T, Q8, 256, 16, 4, 1>(r, a, s);
+        else if (v0 == 128) launch_igemm<T, Q8, 128, 16, 4, 1>(r, a, s);
+        else launch_igemm<T, Q8, 64, 16, 4, 1>(r, a, s);
+      } else if (v1 == 32) {
+        if (v0 == 256) launch_igemm<T, Q8, 256, 32, 4, 1>(r, a, s);
+        else if (v0 == 128) launch_igemm<T, Q8, 128, 32, 4, 1>(r, a, s);
+        else launch_igemm<T, Q8, 64, 32, 4, 1>(r, a, s);
+      } else if (v0 == 128) launch_igemm<T, Q8, 128, 64, 2, 2>(r, a, s);
+      else if (v0 == 64) launch_igemm<T, Q8, 64, 64, 2, 2>(r, a, s);
+      else launch_igemm<T, Q8, 32, 64, 2, 2>(r, a, s);
+      break;
+    default: launch_conv3x3<T, Q8>(r, a, s);  // conv3x3.hip: YDBL_CONV_HALO, YDBL_CONV_VW
   }
-  if (a.Cout <= 32) {
-    if (blocks(256, 32) >= want) return launch_igemm<T, Q8, 256, 32, 4, 1>(a, pointwise, s);
-    if (blocks(128, 32) >= want) return launch_igemm<T, Q8, 128, 32, 4, 1>(a, pointwise, s);
-    return launch_igemm<T, Q8, 64, 32, 4, 1>(a, pointwise, s);
-  }
-  if (a.Cout <= 64) {
-    if (blocks(128, 64) >= want) return launch_igemm<T, Q8, 128, 64, 2, 2>(a, pointwise, s);
-    if (blocks(64, 64) >= want || (!pointwise && a.K >= 512 && a.P >= 16384))
-      return launch_igemm<T, Q8, 64, 64, 2, 2>(a, pointwise, s);
-    return launch_igemm<T, Q8, 32, 64, 2, 2>(a, pointwise, s);
-  }
-  // Cout > 64: 64-wide column blocks (each workgroup stages half the weight rows; the input tile is read
-  // once per column block, from L2/MALL at these map sizes).  Measured against 128-wide blocks on the
-  // bench workloads: DBL-n bs32 14.82 -> 14.91 k img/s (bs16 graphs: 64->128 @80^2 22.6 -> 19.8 us,
-  // 128->192 @40^2 15.6 -> 12.1 us), DBL-s bs64 7.52 -> 7.57 k, DBL-l 1280 bs8 467 -> 466 (noise).
-  if (blocks(128, 64) >= want) return launch_igemm<T, Q8, 128, 64, 2, 2>(a, pointwise, s);
-  if (blocks(64, 64) >= want) return launch_igemm<T, Q8, 64, 64, 2, 2>(a, pointwise, s);
-  return launch_igemm<T, Q8, 32, 64, 2, 2>(a, pointwise, s);
-}
-
-// Kernel choice: thin-input spatial tile (f16/f32 only), halo tile, wave-split-K, block GEMM.
-template <typename T>
-int halo_ksplit(const ConvArgs<T>& a, int64_t wgs);  // conv3x3.hip
-
-template <typename T, bool Q8>
-static void route(const ConvArgs<T>& a, int kh, bool pw, hipStream_t s) {
-  if constexpr (sizeof(T) == 2 && !Q8) {
-    if (try_conv3x3_vw(a, kh, s)) return;
-  }
-  if (!Q8 && try_tile<T>(a, kh, s)) return;
-  if (try_conv3x3_halo<T, Q8>(a, kh, s)) return;
-  if (try_wsk<T, Q8>(a, pw, s)) return;
-  dispatch_conv<T, Q8>(a, pw, s);
+  // the split-K forms (halo, wave-split-K) wrote partial tiles: summed, with the fused epilogue, by a second kernel
+  if (r.ksplit > 1)
+    splitk_epilogue_kernel<T, Q8><<<(unsigned)cdiv((int64_t)a.P * ((a.Cout + 3) >> 2), 256), 256, 0, s>>>(a);
 }
 
 template <typename T>
-static ConvArgs<T> conv_args(const ydbl_conv_desc* d) {
+static void launch(const ConvRoute& r, const ConvArgs<T>& a0, hipStream_t s) {
+  ConvArgs<T> a = a0;
+  a.ksplit = r.ksplit;
+  if constexpr (sizeof(T) == 2) {
+    if (a.dq) return launch_as<T, true>(r, a, s);
+  }
+  launch_as<T, false>(r, a, s);
+}
+
+// The six YDBL_* switches of the dense conv (ConvSwitches, conv_route.hpp), read here and nowhere else: once per
+// ydbl_conv2d_nhwc / ydbl_conv_workspace / ydbl_conv_route call, so a process can flip one between launches.
+static ConvSwitches conv_switches() {
+  auto is = [](const char* e, char c) { return e && *e == c; };
+  ConvSwitches sw;
+  sw.splitk = !is(getenv("YDBL_SPLITK"), '0');
+  sw.halo_nb2 = !is(getenv("YDBL_HALO_NB"), '1');
+  sw.halo_small = !is(getenv("YDBL_HALO_SMALL"), '0');
+  sw.vw = is(getenv("YDBL_VW"), '1');
+  sw.wsk_half = !is(getenv("YDBL_WSK_HALF"), '0');
+  sw.epi_generic = is(getenv("YDBL_EPI_GENERIC"), '1');
+  return sw;
+}
+
+template <typename T>
+static ConvArgs<T> conv_args(const ydbl_conv_desc* d, const ConvSwitches& sw) {
   ConvArgs<T> a{};
   a.x = reinterpret_cast<const T*>(d->x.ptr);
   a.xcs = d->x.cs; a.N = d->x.n; a.H = d->x.h; a.W = d->x.w; a.Cin = d->x.c;
@@ -750,7 +660,7 @@ static ConvArgs<T> conv_args(const ydbl_conv_desc* d) {
   a.KW = d->kw; a.S = d->stride; a.PAD = d->pad; a.DIL = d->dil;
   a.K = d->kh * d->kw * d->x.c; a.KPAD = d->kpad;
   a.act = d->act; a.res = d->res_mode;
-  a.epi_generic = epi_generic();
+  a.epi_generic = sw.epi_generic;
   a.P = d->y.n * d->y.h * d->y.w;
   a.y2 = reinterpret_cast<T*>(d->y2.ptr); a.y2cs = d->y2.cs;
   a.r2 = reinterpret_cast<const T*>(d->r2.ptr); a.r2cs = d->r2.cs;
@@ -761,19 +671,21 @@ static ConvArgs<T> conv_args(const ydbl_conv_desc* d) {
   return a;
 }
 
-ConvArgs<_Float16> conv_args_f16(const ydbl_conv_desc* d) { return conv_args<_Float16>(d); }
+// The route of a valid descriptor.  unlimited: with all the workspace it asks for, whatever it carries.
+template <typename T>
+static ConvRoute desc_route(const ydbl_conv_desc* d, const ConvSwitches& sw, bool unlimited, ConvArgs<T>& a) {
+  a = conv_args<T>(d, sw);
+  // (unlimited: any non-null pointer, nothing is launched from these arguments)
+  if (unlimited) { a.ws = reinterpret_cast<float*>(d->y.ptr); a.ws_bytes = INT64_MAX; }
+  const bool pw = d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0 && d->x.h == d->y.h && d->x.w == d->y.w;
+  return conv_route(a, d->kh, pw, d->dq != nullptr, sw);
+}
 
 template <typename T>
 static int run_conv(const ydbl_conv_desc* d, hipStream_t s) {
-  const ConvArgs<T> a = conv_args<T>(d);
-  const bool pw = d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0 && d->x.h == d->y.h && d->x.w == d->y.w;
-  if constexpr (sizeof(T) == 2) {
-    if (d->dq) {
-      route<T, true>(a, d->kh, pw, s);
-      return check_launch("ydbl_conv2d_nhwc");
-    }
-  }
-  route<T, false>(a, d->kh, pw, s);
+  ConvArgs<T> a;
+  const ConvRoute r = desc_route(d, conv_switches(), false, a);
+  launch(r, a, s);
   return check_launch("ydbl_conv2d_nhwc");
 }
 
@@ -820,24 +732,20 @@ extern "C" int ydbl_conv2d_nhwc(const ydbl_conv_desc* d, void* stream) {
   return d->x.dtype == YDBL_F16 ? run_conv<_Float16>(d, s) : run_conv<float>(d, s);
 }
 
-// Split-K scratch the wave-split-K path would use for this descriptor (0: it would not split).  Computed as if the
-// conv took that path; a conv routed to another kernel ignores its workspace.
 template <typename T>
-static int64_t conv_ws_t(const ydbl_conv_desc* d) {
-  const ConvArgs<T> a = conv_args<T>(d);
-  int64_t need = 0;
-  if (wsk_applies(a)) {
-    int bm, bn;
-    wsk_tiles(a, bm, bn);
-    need = wsk_ws_bytes(a, wsk_ksplit(a, bm, bn));
-  }
-  if (d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->dil == 1 && (int64_t)a.P < 25600) {
-    const int64_t wgs = (int64_t)a.N * cdiv(a.Ho, 8) * cdiv(a.Wo, 16) * cdiv(a.Cout, 32);
-    need = std::max(need, wsk_ws_bytes(a, halo_ksplit(a, wgs)));
-  }
-  return need;
+static void query_route(const ydbl_conv_desc* d, ydbl_conv_route_info* out) {
+  const ConvSwitches sw = conv_switches();
+  ConvArgs<T> a;
+  *out = desc_route(d, sw, false, a);
+  out->workspace_bytes = desc_route(d, sw, true, a).workspace_bytes;
+}
+extern "C" int ydbl_conv_route(const ydbl_conv_desc* d, ydbl_conv_route_info* out) {
+  if (const int rc = conv_check(d)) return rc;
+  if (!out) return fail(YDBL_EINVAL, "conv route: null out");
+  d->x.dtype == YDBL_F16 ? query_route<_Float16>(d, out) : query_route<float>(d, out);
+  return YDBL_OK;
 }
 extern "C" int64_t ydbl_conv_workspace(const ydbl_conv_desc* d) {
-  if (conv_check(d)) return -1;
-  return d->x.dtype == YDBL_F16 ? conv_ws_t<_Float16>(d) : conv_ws_t<float>(d);
+  ydbl_conv_route_info r;
+  return ydbl_conv_route(d, &r) ? -1 : r.workspace_bytes;
 }

@@ -16,11 +16,7 @@
 // bank quads for any starting pixel, and the mixed-g lane groups of ds_read_b128
 // ({0-3,12-15,20-27}, ...) stay conflict-free; weights are [co/16][tap][g][co%16] for the same
 // reason.  Fused epilogue (bias, SiLU, residual add, channel-slice store) from conv_common.hpp.
-#include <stdlib.h>
-
-#include <algorithm>
-
-#include "conv_common.hpp"
+#include "conv_route.hpp"
 
 namespace ydbl {
 
@@ -197,115 +193,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvArgs<T> p, int
   conv_epilogue<T, NTN, NB * TMW, Q8>(p, acc, pp, pv, co, s_bias, co0);
 }
 
-template <typename T, bool Q8>
-void launch_splitk_epilogue(const ConvArgs<T>& a, hipStream_t s);  // conv.hip
-
-// Split-K of the halo kernel for the deep-K stride-1 convs on small maps (fewer than 25600 output pixels: the 40^2
-// maps of a bs4 sub-batch), where a workgroup per tile leaves the chip idle behind a long serial chunk chain
-// (DBL-s 768->128 @40^2 bs4: 24 chunks; on the wave-split-K kernel it took 53.7 us, its 32-pixel tiles re-reading the
-// whole weight slice 200 times): up to 4 workgroups per tile over the input-channel chunks, >= 3 chunks each,
-// toward 512 workgroups; the partials summed in split order by the epilogue kernel.
-constexpr int HALO_SPLIT_MIN_CHUNKS = 8;
-template <typename T>
-int halo_ksplit(const ConvArgs<T>& a, int64_t wgs) {
-  const char* e = getenv("YDBL_SPLITK");
-  if (sizeof(T) != 2 || (e && *e == '0') || (int64_t)a.P >= 25600) return 1;  // fp16 only (conv.hip wsk_ksplit)
-  const int nch = a.Cin / (4 * Vec<T>::N);
-  if (nch < HALO_SPLIT_MIN_CHUNKS) return 1;
-  int k = (int)std::min<int64_t>(4, (512 + wgs - 1) / wgs);
-  while (k > 1 && nch / k < 3) --k;
-  return k;
-}
-
-template <typename T, bool Q8, int S>
-static void launch_halo(const ConvArgs<T>& a0, hipStream_t s) {
-  ConvArgs<T> a = a0;
-  const int tiles_x = (int)cdiv(a.Wo, 16), tiles_y = (int)cdiv(a.Ho, HALO_TH);
-  const int64_t ntiles = (int64_t)a.N * tiles_y * tiles_x;
-  a.ksplit = 1;
-  if (S == 1 && (int64_t)a.P < 25600) {  // (the split's own tiling: 32-channel slices below)
-    a.ksplit = halo_ksplit(a, ntiles * cdiv(a.Cout, 32));
-    if (a.ksplit > 1 && (!a.ws || a.ws_bytes < (int64_t)a.ksplit * a.P * ((a.Cout + 3) & ~3) * 4)) a.ksplit = 1;
-    if (a.ksplit > 1) {
-      const int cs = (int)cdiv(a.Cout, 32);
-      conv3x3_halo_kernel<T, S, 2, Q8><<<dim3((unsigned)(ntiles * cs), (unsigned)a.ksplit), 256, 0, s>>>(
-          a, tiles_x, tiles_y, cs);
-      launch_splitk_epilogue<T, Q8>(a, s);
-      return;
-    }
-  }
-  // Fewer than 400 64-channel workgroups (the 40^2 head convs of a bs16 sub-batch graph: 240) leave
-  // most CUs with one workgroup; 32-channel slices double the grid (conv_bench.py bs16: 384->64 @40^2
-  // 40.5 -> 29.5 us, 192->64 22.8 -> 17.3 us; at bs32, 480 workgroups, they lose: 49.2 -> 52.1 us)
-  // (512: the 64->128 @40^2 head convs of a bs16 graph, 480 workgroups, also gain: 14.3 -> 13.2 us, kbench;
-  // 16-channel slices and 4-row tiles lose on every head shape: profiles/r05/r05_halo_tile_ab.txt)
-  constexpr int64_t n2_below = 512;
-  // 8-row stride-1 tiles of two images per workgroup (N-blocking), 32-channel slices: half the weight staging per
-  // output; each launch takes longer, but with less CU time the two sub-batch branches overlap better -- DBL-n bs32
-  // +0.8 %, DBL-s bs64 / DBL-l 1280 bs8 +0.4 %, DBL-s bs8 even (profiles/r06/r06_fusion_switch_sweep.txt,
-  // r06_sweep2.txt; per launch in graph at bs16: 384->64 @40^2 28.3 -> 33.5 us, 192->64 17.6 -> 20.2).
-  // YDBL_HALO_NB=1 (read per launch; A/B switch): one image per workgroup.
-  if constexpr (S == 1 && !Q8) {
-    // (four images per workgroup, or two in 64-channel slices: DBL-n bs32 -3.1 / -2.3 %, r06_sweep3_cumask.txt)
-    const char* e = getenv("YDBL_HALO_NB");
-    if (!(e && *e == '1') && a.N >= 2) {
-      const int64_t nt2 = (int64_t)(a.N + 1) / 2 * tiles_y * tiles_x;
-      const int cs = (int)cdiv(a.Cout, 32);
-      conv3x3_halo_kernel<T, S, 2, Q8, 2><<<(unsigned)(nt2 * cs), 256, 0, s>>>(a, tiles_x, tiles_y, cs);
-      return;
-    }
-  }
-  if (a.Cout <= 32) {
-    conv3x3_halo_kernel<T, S, 2, Q8><<<(unsigned)ntiles, 256, 0, s>>>(a, tiles_x, tiles_y, 1);
-  } else if (ntiles * cdiv(a.Cout, 64) < n2_below) {
-    const int cs = (int)cdiv(a.Cout, 32);
-    conv3x3_halo_kernel<T, S, 2, Q8><<<(unsigned)(ntiles * cs), 256, 0, s>>>(a, tiles_x, tiles_y, cs);
-  } else {
-    const int cs = (int)cdiv(a.Cout, 64);
-    conv3x3_halo_kernel<T, S, 4, Q8><<<(unsigned)(ntiles * cs), 256, 0, s>>>(a, tiles_x, tiles_y, cs);
-  }
-}
-
+// The halo instance a route names (conv_route.hpp route_halo: stride S, r.v[1] images per workgroup, r.v[2]-channel
+// slices; ksplit > 1: workgroup (x, z) writes split z's partial tile).
 // (One chunk in flight: a register ring of two or three was slower on every head shape, kbench bs16 1 / 2 / 3
 // chunks: 384->64 @40^2 26.6 / 28.8 / 31.3 us, 256->32 @80^2 28.4 / 32.8 / 47.1, 64->128 @40^2 12.9 / 17.1 / 19.9.)
-
-// 3x3, pad 1, dil 1, stride 1/2, Cin a multiple of BK and >= 2 chunks.  Returns false when the
-// shape is not this kernel's (the caller falls back to the implicit-GEMM kernels).
-// Where the halo tile beats the implicit GEMM (scripts/conv_bench.py, fp16, MI355X): stride 1 on
-// >= 51200 output pixels.  Measured: 256->32 @80^2 bs32 132 -> 62 us, 512->64 @80^2 bs64
-// 714 -> 382 us, 768->128 @40^2 bs64 534 -> 348 us, 1024->128 @160^2 bs8 1371 -> 688 us.
-template <typename T, bool Q8>
-bool try_conv3x3_halo(const ConvArgs<T>& a, int kh, hipStream_t s) {
-  constexpr int BK = 4 * Vec<T>::N;
-  // Stride 2 on >= 204800 output pixels: 8-row tiles over a (2*8+1) x 33 halo (A/B against the block
-  // GEMM: DBL-l 128->256 @320 bs8 442 -> 341 us).  Smaller maps stay on the block GEMM: 128->128 @40 bs32
-  // 17.8 vs 24.7 us, and DBL-n's 64->64 @80 bs32 (18.8 vs 17.5 us alone) cost the whole step ~40 us.
-  if (kh == 3 && a.KW == 3 && a.PAD == 1 && a.DIL == 1 && a.S == 2 && a.Cin % BK == 0 &&
-      a.Cin >= 2 * BK && a.xcs % Vec<T>::N == 0 && (int64_t)a.P >= 204800)
-    return launch_halo<T, Q8, 2>(a, s), true;
-  if (kh != 3 || a.KW != 3 || a.PAD != 1 || a.DIL != 1 || a.S != 1) return false;
-  if (a.Cin % BK || a.Cin < 2 * BK || a.xcs % Vec<T>::N) return false;
-  // 51200 output pixels (40^2 x 32) was the measured crossover at bs32; the bench's two bs16 sub-batch
-  // graphs put the 40^2 head convs at 25600, where the halo tile still wins (DBL-n bs32 on two streams
-  // 13.7 k -> 14.1 k img/s; 12800 loses again: 14.0 k)
-  if ((int64_t)a.P < 25600) {  // small maps: only as the split-K form (halo_ksplit), with room for its partials
-    const int64_t wgs = (int64_t)a.N * cdiv(a.Ho, 8) * cdiv(a.Wo, 16) * cdiv(a.Cout, 32);
-    const int k = halo_ksplit(a, wgs);
-    if ((int64_t)a.P < 4096) return false;
-    if (k >= 2 && a.ws && a.ws_bytes >= (int64_t)k * a.P * ((a.Cout + 3) & ~3) * 4) return launch_halo<T, Q8, 1>(a, s), true;
-    // Too few chunks to split (Cin < 256) and wide Cout: the wave-split-K kernel's 32x128 tiles would re-read the
-    // whole weight matrix once per 32 pixels (DBL-s bs4: 128->256 @40^2, 200 tile rows x 590 KB); the halo tile in
-    // 32-channel slices reads it once per 128 pixels
-    // (YDBL_HALO_SMALL=0, read per launch: the wave-split-K route, A/B switch)
-    const char* e = getenv("YDBL_HALO_SMALL");
-    if (k < 2 && a.Cout >= 128 && !(e && *e == '0')) return launch_halo<T, Q8, 1>(a, s), true;
-    return false;
+template <typename T, bool Q8, int S>
+static void launch_halo(const ConvRoute& r, const ConvArgs<T>& a, hipStream_t s) {
+  const int tiles_x = (int)cdiv(a.Wo, 16), tiles_y = (int)cdiv(a.Ho, HALO_TH), cs = (int)cdiv(a.Cout, r.v[2]);
+  const dim3 grid(r.grid[0], r.grid[1]);
+  if constexpr (S == 1 && !Q8) {
+    if (r.v[1] == 2) return conv3x3_halo_kernel<T, S, 2, Q8, 2><<<grid, 256, 0, s>>>(a, tiles_x, tiles_y, cs);
   }
-  // No 4-row tiles: every workgroup re-reads all of its channels' weights, so at 480 8-row tiles (40^2 bs32,
-  // Cout 64) the doubled grid lost (A/B: 384->64 88.9 vs 49.6 us, 192->64 45.9 vs 28.0 us); 384->64 @40^2 also
-  // beats the wave-split-K kernel it used to take (78.8 us).
-  launch_halo<T, Q8, 1>(a, s);
-  return true;
+  if (r.v[2] == 32) conv3x3_halo_kernel<T, S, 2, Q8><<<grid, 256, 0, s>>>(a, tiles_x, tiles_y, cs);
+  else conv3x3_halo_kernel<T, S, 4, Q8><<<grid, 256, 0, s>>>(a, tiles_x, tiles_y, cs);
 }
 
 // ---- VGPR-weight 3x3 (fp16, stride 1, Cin 32..128): the bneck.hip layout for a single conv ----------
@@ -409,49 +309,23 @@ __global__ __launch_bounds__(256, 2) void conv3x3_vw_kernel(ConvArgs<_Float16> p
   }
 }
 
-// TH16 > 0: 16-row tiles (ROWS16 rows per pass) when the map gives >= 1024 of them (half the halo
-// re-reads of 8-row tiles); only configurations that stay spill-free at 16 rows have one.
-template <int CIN, int TPW, int NWG, int ROWS8, int ROWS16 = 0>
-static void launch_vw(const ConvArgs<_Float16>& a, int cs, hipStream_t s) {
-  const int tiles_x = (int)cdiv(a.Wo, 16);
-  const int64_t t16 = (int64_t)a.N * cdiv(a.Ho, 16) * tiles_x;
-  if constexpr (ROWS16 > 0) {
-    if (t16 >= 1024) {
-      const int tiles_y = (int)cdiv(a.Ho, 16), nt = a.N * tiles_y * tiles_x;
-      conv3x3_vw_kernel<CIN, TPW, NWG, 16, ROWS16><<<(unsigned)(nt * cs), 256, 0, s>>>(a, tiles_x, tiles_y, nt, cs);
-      return;
-    }
+// The VGPR-weight instance a route names (conv_route.hpp route_vw): 8-row tiles, one output-channel slice.
+template <int CIN, int TPW, int NWG, int ROWS>
+static void launch_vw(const ConvRoute& r, const ConvArgs<_Float16>& a, hipStream_t s) {
+  const int tiles_x = (int)cdiv(a.Wo, 16), tiles_y = (int)cdiv(a.Ho, 8);
+  conv3x3_vw_kernel<CIN, TPW, NWG, 8, ROWS><<<r.grid[0], 256, 0, s>>>(a, tiles_x, tiles_y, a.N * tiles_y * tiles_x, 1);
+}
+
+template <typename T, bool Q8>
+void launch_conv3x3(const ConvRoute& r, const ConvArgs<T>& a, hipStream_t s) {
+  if constexpr (sizeof(T) == 2 && !Q8) {
+    if (r.family == YDBL_CONV_VW) return r.v[0] == 128 ? launch_vw<128, 1, 4, 2>(r, a, s) : launch_vw<64, 2, 2, 4>(r, a, s);
   }
-  const int tiles_y = (int)cdiv(a.Ho, 8), nt = a.N * tiles_y * tiles_x;
-  conv3x3_vw_kernel<CIN, TPW, NWG, 8, ROWS8><<<(unsigned)(nt * cs), 256, 0, s>>>(a, tiles_x, tiles_y, nt, cs);
+  if (r.v[0] == 1) launch_halo<T, Q8, 1>(r, a, s);
+  else launch_halo<T, Q8, 2>(r, a, s);
 }
-
-// fp16 3x3 stride-1 pad-1 convs routed to the VGPR-weight kernel; false when the shape is not one of
-// them.  TPW output-channel tiles per wave, NWG wave groups over the channels (4 / NWG waves split the
-// rows): combinations that fit 256 VGPRs without scratch (scripts/kres.py).
-// Only the shapes where it measured faster than the halo / block-GEMM / tile kernels (conv_bench.py,
-// bs32, MI355X): 128->64 @40^2 32.3 -> 21.3 us, 64->64 @40^2 20.0 -> 16.5 us.  Every workgroup loads
-// all of its channels' weights into VGPRs, so on 80^2 maps (1600 workgroups) and for Cout 32/128 the
-// re-read loses (measured with the kernel open to Cin/Cout 32..128: 64->64 @80^2 41.7 -> 47.9,
-// 64->32 @80^2 22.5 -> 39.5, 64->128 @40^2 26.0 -> 29.4, 64->64 @20^2 8.9 -> 10.0 us).
-bool try_conv3x3_vw(const ConvArgs<_Float16>& a, int kh, hipStream_t s) {
-  if (kh != 3 || a.KW != 3 || a.PAD != 1 || a.DIL != 1 || a.S != 1) return false;
-  // Round 6: off by default -- the N-blocked halo tile takes these shapes (DBL-n bs32 +0.4 %, DBL-s bs8 +0.7 %, bs64
-  // +1.5 %, profiles/r06/r06_conv_route_sweep.txt: less CU time per image in the two-branch layout, though each launch
-  // is longer).  YDBL_VW=1 (read per launch) routes them here.
-  const char* e = getenv("YDBL_VW");
-  if (!(e && *e == '1')) return false;
-  if (a.xcs % 8 || a.H != a.Ho || a.W != a.Wo || (int64_t)a.N * a.Ho * a.Wo >= (1LL << 31)) return false;
-  if (a.Cin == 128 && a.Cout == 64) return launch_vw<128, 1, 4, 2>(a, 1, s), true;
-  constexpr int64_t vw_min = 25601;
-  if (a.Cin == 64 && a.Cout == 64 && a.P >= vw_min && a.P <= 65536) return launch_vw<64, 2, 2, 4>(a, 1, s), true;
-  return false;
-}
-
-template int halo_ksplit<_Float16>(const ConvArgs<_Float16>&, int64_t);
-template int halo_ksplit<float>(const ConvArgs<float>&, int64_t);
-template bool try_conv3x3_halo<_Float16, false>(const ConvArgs<_Float16>&, int, hipStream_t);
-template bool try_conv3x3_halo<_Float16, true>(const ConvArgs<_Float16>&, int, hipStream_t);
-template bool try_conv3x3_halo<float, false>(const ConvArgs<float>&, int, hipStream_t);
+template void launch_conv3x3<_Float16, false>(const ConvRoute&, const ConvArgs<_Float16>&, hipStream_t);
+template void launch_conv3x3<_Float16, true>(const ConvRoute&, const ConvArgs<_Float16>&, hipStream_t);
+template void launch_conv3x3<float, false>(const ConvRoute&, const ConvArgs<float>&, hipStream_t);
 
 }  // namespace ydbl

@@ -117,11 +117,6 @@ __device__ __forceinline__ int hslot(int pix, int g) {
   return (pix / (16 * S)) * (64 * S) + g * (16 * S) + (pix % S) * 16 + ((pix / S) & 15);
 }
 
-// conv3x3.hip: halo-tiled 3x3 kernel for Cin >= 2 k-steps; false when the shape is not its own.
-template <typename T, bool Q8>
-bool try_conv3x3_halo(const ConvArgs<T>& a, int kh, hipStream_t s);
-// conv3x3.hip: fp16 3x3 stride-1 convs with Cin 32..128 and VGPR-resident weights.
-bool try_conv3x3_vw(const ConvArgs<_Float16>& a, int kh, hipStream_t s);
 // dsc_lean.hip: one-round-trip DSConv / DWConv->Conv1x1 for the small-map shapes it is built for.
 // dsconv.hip: a ydbl_dsconv_desc's kernel arguments (fp16) and its descriptor rules (YDBL_OK or the error code).
 ConvArgs<_Float16> ds_args_f16(const ydbl_dsconv_desc* d);

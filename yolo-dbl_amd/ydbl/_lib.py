@@ -34,6 +34,15 @@ class ConvDesc(C.Structure):
                 ("dq", C.c_void_p), ("qscale", C.c_float), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class ConvRouteInfo(C.Structure):
+    """ydbl_conv_route_info: what ydbl_conv2d_nhwc would launch for a descriptor (include/ydbl.h ydbl_conv_route)."""
+    _fields_ = [("family", C.c_int32), ("v", C.c_int32 * 4), ("pointwise", C.c_int32), ("ksplit", C.c_int32),
+                ("epi", C.c_int32), ("grid", C.c_uint32 * 3), ("workspace_bytes", C.c_int64)]
+
+
+CONV_VW, CONV_TILE, CONV_HALO, CONV_WSK, CONV_IGEMM = range(5)
+
+
 class DwConvDesc(C.Structure):
     _fields_ = [("x", View), ("y", View), ("r", View), ("w", C.c_void_p), ("bias", C.c_void_p),
                 ("kh", C.c_int32), ("kw", C.c_int32), ("stride", C.c_int32), ("pad", C.c_int32), ("dil", C.c_int32),
@@ -261,6 +270,7 @@ SIGNATURES = {
     "ydbl_pred_candidates": ([C.POINTER(PredCandDesc), _P], C.c_int),
     "ydbl_nms_workspace": ([C.c_int32, C.c_int32, C.c_int32], C.c_int64),
     "ydbl_conv_workspace": ([C.POINTER(ConvDesc)], C.c_int64),
+    "ydbl_conv_route": ([C.POINTER(ConvDesc), C.POINTER(ConvRouteInfo)], C.c_int),
     "ydbl_nms": ([C.POINTER(NmsDesc), _P], C.c_int),
     "ydbl_conv_stem2_params_size": ([C.c_int32], C.c_int64),
     "ydbl_conv_stem2_pack": ([_P, _P, _P, _P, C.c_int32, _P], C.c_int),
