@@ -525,6 +525,51 @@ typedef struct {
 int64_t ydbl_nms_workspace(int32_t n, int32_t cap, int32_t max_nms);
 int ydbl_nms(const ydbl_nms_desc* d, void* stream);
 
+/* The end2end (YOLOv10, v10Detect) head: no NMS, a top-k.
+ *
+ * ydbl_detect_decode_e2e: ydbl_detect_decode for a head with end2end = True (nn/modules/head.py:120-141, :196-198):
+ * decode_bboxes calls dist2bbox(..., xywh=False), so a box is x1 = (ax - l) * stride, y1 = (ay - t) * stride,
+ * x2 = (ax + r) * stride, y2 = (ay + b) * stride in fp32 and in that order of operations -- never xywh converted
+ * back.  y_ref, when given, is the end2end layout [n][4+nc][A] with those xyxy rows; the candidate boxes are the same
+ * four values.  Everything else (scores, filter, lists, counters) is ydbl_detect_decode's.
+ *
+ * ydbl_detect_topk: Detect.postprocess (head.py:200-221: the k anchors of largest best-class score, then the k largest
+ * of their k * nc scores, k = min(max_det, A) with the head's own max_det = 300) followed by the six-column branch
+ * of non_max_suppression (utils/ops.py:224-228: score > conf_thres, [:max_det], then the `classes` filter), over the
+ * multi-label candidate lists of the decode (cand_idx = anchor * nc + cls, already thresholded by conf).  With
+ * distinct scores the two chained topk's are the k largest of all (anchor, class) scores: a pair of an anchor outside
+ * the first top-k has k pairs at least as large ahead of it.  Where scores tie torch.topk's order is unspecified;
+ * OUR PINNED RULE is (score descending, cand_idx ascending), i.e. the smaller anchor, then the smaller class.
+ * Per image: the first min(k_head, max_det) candidates in that order (k_head = min(head max_det, A), the caller's),
+ * then, with classes != NULL, the rows whose class is not listed are dropped and the gaps closed, order kept -- the
+ * filter comes after the cut, as in the reference.  iou, agnostic, multi_label, max_nms and max_wh play no part.
+ * out / out_count, out_stride / count_stride and clip_w / clip_h: the contract of ydbl_nms_desc (rows
+ * x1,y1,x2,y2,score,cls in selection order, rows past the count up to max_det zeroed, out_stride floats between
+ * images), 1 <= max_det <= 4096.  cand_idx must be distinct within an image and scores positive (their bit patterns
+ * then order like the values).  Nothing is sorted but the survivors: a radix select over 8-bit digits of the key
+ * (score bits inverted | cand_idx) finds the k-th key, the <= k survivors are ranked in LDS.  per_image (schedule
+ * only, same output): nonzero = one workgroup per image reads the list itself (predict thresholds: hundreds of
+ * candidates); 0 = three launches ahead of it, split over the list (a chip-wide histogram of the score's exponent and
+ * top mantissa bits, then a compaction of the bins that can hold a survivor), for validation's conf 0.001 and the
+ * unthresholded A * nc candidates of DetectionModel.forward.  The histogram is summed with integer atomics and the
+ * survivors are ordered by key, so the output is bit-identical from run to run.  workspace: caller-owned,
+ * ydbl_detect_topk_workspace(n, cap) bytes, uninitialised memory is fine. */
+int ydbl_detect_decode_e2e(const ydbl_decode_desc* d, void* stream);
+typedef struct {
+  const float* cand_box; const float* cand_score; const int32_t* cand_cls; const int32_t* cand_idx;
+  const int32_t* cand_count;
+  int32_t n, cap;
+  int32_t k_head, max_det;
+  const int32_t* classes; int32_t nclasses;
+  float clip_w, clip_h;
+  float* out; int32_t* out_count;
+  int64_t out_stride, count_stride;
+  void* workspace; int64_t workspace_bytes;
+  int32_t per_image;
+} ydbl_topk_desc;
+int64_t ydbl_detect_topk_workspace(int32_t n, int32_t cap);
+int ydbl_detect_topk(const ydbl_topk_desc* d, void* stream);
+
 /* Stem pair (fp16): y = SiLU(conv3x3_s2(SiLU(conv3x3_s1(x * scale) + b0)) + b1), NHWC [n][ceil(h/2)][ceil(w/2)][2*c0],
  * from the NCHW fp32 batch x [n][3][h][w]; the full-resolution intermediate never leaves LDS.
  * params: device blob of ydbl_conv_stem2_params_size(c0) bytes filled on the HOST by

@@ -3,9 +3,10 @@ scripts/ab_bench.py), and the two kernels the YOLO11 / YOLOv8 baselines add, alo
 
     python scripts/baseline_bench.py [--batch 32] [--imgsz 640] [--rounds 5] [--steps 40]
 
-Legs: yolo11n, yolov8n, yolov13n (tests/golden/*.json layer tables, nc 3, weights seeded: torch.manual_seed(0) +
+Legs: yolo11n, yolov8n, yolov10n, yolov13n (tests/golden/*.json layer tables, nc 3, weights seeded: torch.manual_seed(0) +
 trained_like_) and DBL-n (the bench fixture), each model.session(batch, imgsz, imgsz, half=True, streams=2): the
-two-branch session bench.py measures.  Figures, not claims: no host reference run exists to form a ratio.
+two-branch session bench.py measures (yolov10n's tail is the end2end decode and ydbl_detect_topk, the others' the
+NMS).  Figures, not claims: no host reference run exists to form a ratio.
 
 Then, from sub-batch plan 0 of yolo11n (batch / 2 images): the in-graph time of SPPF.pool5x3 and PSA.attn
 (Plan.run_graph_timed) against the bytes each moves, and ydbl_psa_attn alone against eager torch
@@ -100,7 +101,7 @@ def main():
 
     x = blob_images(a.batch, a.imgsz, seed=1234).cuda()
     sess = {}
-    for name in ("yolo11n", "yolov8n", "yolov13n", "DBL-n"):
+    for name in ("yolo11n", "yolov8n", "yolov10n", "yolov13n", "DBL-n"):
         s = build(name).session(a.batch, a.imgsz, a.imgsz, half=True, conf=0.25, iou=0.7, streams=2)
         s.load(x)
         for _ in range(5):

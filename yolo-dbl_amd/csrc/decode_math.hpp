@@ -81,6 +81,14 @@ __device__ __forceinline__ Xywh dist2xywh(int gx, int gy, const float (&dist)[4]
   return o;
 }
 
+// dist2bbox(xywh=False) * stride, the end2end head's decode (head.py:196-198, utils/tal.py:333-357): the corners
+// straight from the distances, (anchor -+ dist) * stride, never through xywh
+__device__ __forceinline__ f32x4 dist2xyxy(int gx, int gy, const float (&dist)[4], float st) {
+#pragma clang fp contract(off)
+  const float ax = float(gx) + 0.5f, ay = float(gy) + 0.5f;
+  return f32x4{(ax - dist[0]) * st, (ay - dist[1]) * st, (ax + dist[2]) * st, (ay + dist[3]) * st};
+}
+
 // xywh2xyxy (U/utils/ops.py:416-433)
 __device__ __forceinline__ f32x4 xywh2xyxy(const Xywh& v) {
 #pragma clang fp contract(off)
@@ -135,7 +143,8 @@ __device__ __forceinline__ void cand_write_nobox(const CandSink& k, int b, int s
 //   pos     the anchor's candidate index (pos * nc + class when multi-label)
 // DEFER (the sparse box path): same filter, same scores, same slots, but no box is read or written; a quad that holds
 // a candidate stores 1 into *tile, the mask byte of the anchor's 8 x 16 tile (racing quads store the same value).
-template <typename T, int QS, bool DEFER = false, typename F>
+// XYXY: the end2end head's boxes (dist2xyxy).
+template <typename T, int QS, bool DEFER = false, bool XYXY = false, typename F>
 __device__ __forceinline__ void quad_candidates(const CandSink& k, int b, int s, bool ok, int nc, F&& logit,
                                                 const T* bp, int gx, int gy, float st, int pos,
                                                 unsigned char* tile = nullptr) {
@@ -183,7 +192,8 @@ __device__ __forceinline__ void quad_candidates(const CandSink& k, int b, int s,
     float dist[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) dist[i] = __shfl(mine, q0 + i * QS);
-    box = xywh2xyxy(dist2xywh(gx, gy, dist, st));
+    if constexpr (XYXY) box = dist2xyxy(gx, gy, dist, st);
+    else box = xywh2xyxy(dist2xywh(gx, gy, dist, st));
     if (k.multi) {
       for (int j = s; j < nc; j += 4) {
         const float sc = cls_score(logit(j));

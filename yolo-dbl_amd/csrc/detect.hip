@@ -56,7 +56,9 @@ struct AugArgs {
   int a_lo, a_hi, pos_base, ystride;
 };
 
-template <typename T, bool AUG>
+// E2E: the end2end head (include/ydbl.h ydbl_detect_decode_e2e): xyxy boxes straight from the distances, in y_ref
+// and in the candidates.
+template <typename T, bool AUG, bool E2E = false>
 __device__ __forceinline__ void decode_body(const DecodeArgs<T>& p, const AugArgs& g) {
   const int b = blockIdx.y;
   const int tq = blockIdx.x * blockDim.x + threadIdx.x;
@@ -76,7 +78,8 @@ __device__ __forceinline__ void decode_body(const DecodeArgs<T>& p, const AugArg
   const CandSink& k = p.k;
   if constexpr (!AUG) {
     if (!p.yref) {
-      quad_candidates<T, 1>(k, b, s, true, p.nc, [&](int j) { return float(cp[j]); }, bp, gx, gy, p.stride[l], a);
+      quad_candidates<T, 1, false, E2E>(k, b, s, true, p.nc, [&](int j) { return float(cp[j]); }, bp, gx, gy,
+                                        p.stride[l], a);
       return;
     }
   }
@@ -96,11 +99,14 @@ __device__ __forceinline__ void decode_body(const DecodeArgs<T>& p, const AugArg
     A = g.ystride;
     pos = g.pos_base + (a - g.a_lo);
   }
+  f32x4 box;
+  if constexpr (E2E) box = dist2xyxy(gx, gy, dist, p.stride[l]);
+  else box = xywh2xyxy(v);
   if (p.yref) {
     float* yr = p.yref + (int64_t)b * (4 + p.nc) * A + pos;
-    yr[s * A] = s == 0 ? v.cx : s == 1 ? v.cy : s == 2 ? v.w : v.h;
+    if constexpr (E2E) yr[s * A] = s == 0 ? box[0] : s == 1 ? box[1] : s == 2 ? box[2] : box[3];
+    else yr[s * A] = s == 0 ? v.cx : s == 1 ? v.cy : s == 2 ? v.w : v.h;
   }
-  const f32x4 box = xywh2xyxy(v);
   float best = -1.f;
   int bj = 0;
   for (int j = s; j < p.nc; j += 4) {
@@ -123,6 +129,10 @@ __device__ __forceinline__ void decode_body(const DecodeArgs<T>& p, const AugArg
 template <typename T>
 __global__ __launch_bounds__(256) void decode_kernel(DecodeArgs<T> p) {
   decode_body<T, false>(p, AugArgs{});
+}
+template <typename T>
+__global__ __launch_bounds__(256) void decode_e2e_kernel(DecodeArgs<T> p) {
+  decode_body<T, false, true>(p, AugArgs{});
 }
 template <typename T>
 __global__ __launch_bounds__(256) void decode_aug_kernel(DecodeArgs<T> p, AugArgs g) {
@@ -1207,7 +1217,7 @@ static DView<const T> cvw(const ydbl_view& v) {
 }
 
 template <typename T>
-static int decode_t(const ydbl_decode_desc* d, const ydbl_decode_aug* g, hipStream_t s) {
+static int decode_t(const ydbl_decode_desc* d, const ydbl_decode_aug* g, hipStream_t s, bool e2e) {
   DecodeArgs<T> a{};
   int A = 0;
   for (int l = 0; l < d->nl; ++l) {
@@ -1223,6 +1233,11 @@ static int decode_t(const ydbl_decode_desc* d, const ydbl_decode_aug* g, hipStre
                  d->conf_thres, d->multi_label, d->classes, d->nclasses};
   const int B = d->box[0].n;
   const dim3 grid((unsigned)cdiv((int64_t)A * 4, 256), B);  // a quad per anchor
+  if (e2e) {
+    zero_counts_kernel<<<1, 256, 0, s>>>(d->cand_count, B);
+    decode_e2e_kernel<T><<<grid, 256, 0, s>>>(a);
+    return check_launch("ydbl_detect_decode_e2e");
+  }
   if (!g) {
     zero_counts_kernel<<<1, 256, 0, s>>>(d->cand_count, B);
     decode_kernel<T><<<grid, 256, 0, s>>>(a);
@@ -1247,7 +1262,7 @@ static int decode_t(const ydbl_decode_desc* d, const ydbl_decode_aug* g, hipStre
 
 using namespace ydbl;
 
-static int decode_entry(const ydbl_decode_desc* d, const ydbl_decode_aug* g, void* stream) {
+static int decode_entry(const ydbl_decode_desc* d, const ydbl_decode_aug* g, void* stream, bool e2e = false) {
   if (!d) return fail(YDBL_EINVAL, "decode: null descriptor");
   if (d->nl < 1 || d->nl > 3) return fail(YDBL_EINVAL, "decode: 1..3 levels");
   for (int l = 0; l < d->nl; ++l) {
@@ -1262,10 +1277,14 @@ static int decode_entry(const ydbl_decode_desc* d, const ydbl_decode_aug* g, voi
   if (!d->cand_box || !d->cand_score || !d->cand_cls || !d->cand_idx || !d->cand_count || d->cap < 1)
     return fail(YDBL_EINVAL, "decode: null candidate buffers");
   hipStream_t s = as_stream(stream);
-  return d->box[0].dtype == YDBL_F16 ? decode_t<_Float16>(d, g, s) : decode_t<float>(d, g, s);
+  return d->box[0].dtype == YDBL_F16 ? decode_t<_Float16>(d, g, s, e2e) : decode_t<float>(d, g, s, e2e);
 }
 
 extern "C" int ydbl_detect_decode(const ydbl_decode_desc* d, void* stream) { return decode_entry(d, nullptr, stream); }
+
+extern "C" int ydbl_detect_decode_e2e(const ydbl_decode_desc* d, void* stream) {
+  return decode_entry(d, nullptr, stream, true);
+}
 
 extern "C" int ydbl_detect_decode_aug(const ydbl_decode_desc* d, const ydbl_decode_aug* g, void* stream) {
   if (!g) return fail(YDBL_EINVAL, "decode_aug: null augmentation record");

@@ -110,6 +110,17 @@ class NmsDesc(C.Structure):
                 ("count_stride", C.c_int64), ("per_image", C.c_int32)]
 
 
+class TopkDesc(C.Structure):
+    """ydbl_topk_desc: the end2end head's selection (Detect.postprocess + the six-column NMS branch) over the decode's
+    multi-label candidate lists; out / out_count as NmsDesc's."""
+    _fields_ = [("cand_box", C.c_void_p), ("cand_score", C.c_void_p), ("cand_cls", C.c_void_p),
+                ("cand_idx", C.c_void_p), ("cand_count", C.c_void_p), ("n", C.c_int32), ("cap", C.c_int32),
+                ("k_head", C.c_int32), ("max_det", C.c_int32), ("classes", C.c_void_p), ("nclasses", C.c_int32),
+                ("clip_w", C.c_float), ("clip_h", C.c_float), ("out", C.c_void_p), ("out_count", C.c_void_p),
+                ("out_stride", C.c_int64), ("count_stride", C.c_int64), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64), ("per_image", C.c_int32)]
+
+
 class InputBind(C.Structure):
     """ydbl_input_bind: device word holding the batch pointer, device fp32 batch maximum (LoadTensor's /255 rule)."""
     _fields_ = [("x", C.c_void_p), ("amax", C.c_void_p)]
@@ -266,6 +277,9 @@ SIGNATURES = {
     "ydbl_dysample2": ([C.POINTER(DySample2Desc), _P], C.c_int),
     "ydbl_detect_decode": ([C.POINTER(DecodeDesc), _P], C.c_int),
     "ydbl_detect_decode_aug": ([C.POINTER(DecodeDesc), C.POINTER(DecodeAug), _P], C.c_int),
+    "ydbl_detect_decode_e2e": ([C.POINTER(DecodeDesc), _P], C.c_int),
+    "ydbl_detect_topk_workspace": ([C.c_int32, C.c_int32], C.c_int64),
+    "ydbl_detect_topk": ([C.POINTER(TopkDesc), _P], C.c_int),
     "ydbl_scale_img": ([C.POINTER(ScaleImgDesc), _P], C.c_int),
     "ydbl_pred_candidates": ([C.POINTER(PredCandDesc), _P], C.c_int),
     "ydbl_nms_workspace": ([C.c_int32, C.c_int32, C.c_int32], C.c_int64),

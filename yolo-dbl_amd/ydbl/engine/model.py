@@ -305,8 +305,20 @@ class Model:
         gains): ydbl_detect_loss behind the head on dense levels, one plan for the whole batch (DetectSession.loss,
         load_labels)."""
         loss = check_loss(loss, augment, gather_rows)
+        if loss is not None:
+            from ..nn.tasks import check_e2e_loss
+
+            check_e2e_loss(self.model)
         embed = check_embed(embed, len(self.model.model), augment, fp8, gather_rows)
         augment = check_augment(augment, fp8, gather_rows)
+        if fp8 and self.model.end2end:  # (DetectSession's guard, ahead of the device lookup)
+            raise NotImplementedError("fp8=True on an end2end (YOLOv10) model: no calibration record exists for the "
+                                      "YOLOv10 baseline")
+        if augment and self.model.end2end:  # _predict_augment (U/nn/tasks.py:361-366): a warning and the plain pass
+            from ..nn.tasks import warn_e2e_augment
+
+            warn_e2e_augment()
+            augment = False
         if loss is not None and embed is not None:
             raise ValueError("loss=True with embed: the truncated plan has no head to score")
         if streams is None:
@@ -684,6 +696,10 @@ class Model:
                 "coco_eval": bool(coco_eval), "loss": bool(loss)}
         check_augment(args["augment"], args["fp8"])
         check_loss(args["loss"], args["augment"], args.get("gather_rows"))
+        if args["loss"]:
+            from ..nn.tasks import check_e2e_loss
+
+            check_e2e_loss(self.model)  # an end2end model's criterion is E2EDetectLoss: before any device work
         self.validator = DetectionValidator(self, args)  # kept: its per-image stats (tp, conf, pred_cls, target_cls)
         return self.validator(data)
 

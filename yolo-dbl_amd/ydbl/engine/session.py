@@ -220,7 +220,7 @@ class DetectSession(BatchSession):
     sparse_box: the session runs the sparse box path (_sparse_box) -- its P3 / P4 box logits exist only
     in the 8 x 16 tiles that hold an NMS candidate of the last batch (see feats())."""
 
-    sparse_box = fused_candidates = False
+    sparse_box = fused_candidates = end2end = False
     records = loss = out_flat = None
 
     def __init__(self, model, batch: int, h: int, w: int, *args, device="cuda", streams=1, gather_rows=None,
@@ -231,6 +231,15 @@ class DetectSession(BatchSession):
         if opt.fp8 and any(type(m).__name__ == "A2C2f" for m in model.modules()):
             raise NotImplementedError("fp8=True on a model with A2C2f: no calibration record exists for the "
                                       "area-attention blocks")
+        # an end2end head (v10Detect): the tail is a top-k, not an NMS (_compile_e2e)
+        self.end2end = bool(getattr(model.model[-1], "end2end", False))
+        if self.end2end and opt.fp8:
+            raise NotImplementedError("fp8=True on an end2end (YOLOv10) model: no calibration record exists for the "
+                                      "YOLOv10 baseline")
+        if self.end2end and opt.loss is not None:
+            from ..nn.tasks import check_e2e_loss
+
+            check_e2e_loss(model)
         if opt.fp8:
             for name in ("C2PSA", "SPPF"):
                 if any(type(m).__name__ == name for m in model.modules()):
@@ -312,6 +321,8 @@ class DetectSession(BatchSession):
         self.A = sum(lv.h * lv.w for lv in cm.levels)
         if self.det is None:
             self._alloc_outputs(self.A)
+        if self.end2end:
+            return self._compile_e2e(cm, plan)
         self._init_tail(plan, self.A)
         dd = self._decode_desc(cm.levels)
         # No decode pass when every level's class conv is the tail of a DWConv -> Conv1x1 launch (DBL-n, nc <= 4,
@@ -327,6 +338,30 @@ class DetectSession(BatchSession):
         self._emit_nms(plan)
         if opt.loss is not None:
             self._emit_loss(plan, cm, dd, opt.loss)
+        return plan
+
+    def _compile_e2e(self, cm, plan: Plan) -> Plan:
+        """The tail of an end2end head (v10Detect; U/nn/modules/head.py:120-141, :200-221 and the six-column branch of
+        non_max_suppression, U/utils/ops.py:224-228): the one2one levels decoded in multi-label mode whatever
+        opt.multi_label and nc are (cap = A * nc, xyxy boxes, score > conf, no `classes` filter), then
+        ydbl_detect_topk where the NMS stands for the other heads -- the first min(min(head.max_det, A), max_det)
+        pairs by (score, anchor * nc + class), the `classes` filter behind the cut.  iou, agnostic, max_nms and max_wh
+        play no part, as in the reference; no fused candidates, no sparse box path.  keep_pred: the dense one2one map
+        [B, 4+nc, A] with xyxy rows.  nms=False: the decode alone."""
+        from ..nn.modules import E2ETail
+
+        opt, head, dev = self.opt, cm.detect, plan.device
+        self.multi_label = True
+        classes = opt.classes
+        self.classes_t = torch.tensor(list(classes), dtype=torch.int32, device=dev) if classes is not None else None
+        tail = self.tail = E2ETail(plan, cm.levels, head.stride.tolist(), self.nc, self.batch, conf=self.conf,
+                                   k_head=min(int(head.max_det), self.A), max_det=self.max_det, det=self.det,
+                                   count=self.count, pred=self.pred, classes=self.classes_t,
+                                   clip=(self.h, self.w) if opt.clip else None,
+                                   per_image=self.conf >= PER_IMAGE_NMS_CONF, topk=bool(opt.nms))
+        self.cap = tail.cap
+        self.cand_box, self.cand_score, self.cand_cls = tail.cand_box, tail.cand_score, tail.cand_cls
+        self.cand_idx, self._cand_count = tail.cand_idx, tail.cand_count
         return plan
 
     # ------------------------------------------------------------------ the detection tail
@@ -497,7 +532,7 @@ class DetectSession(BatchSession):
             p.compiled.set_bind(self.bind_ptrs[k, i:i + 1] if k else None, self.bind_amax[k])
         det = self.det if det is None else det
         count = self.count if count is None else count
-        nds = [st.args[0] for p in parts for st in p.plan.steps if st.fn.__name__ == "ydbl_nms"]
+        nds = [st.args[0] for p in parts for st in p.plan.steps if st.fn.__name__ in ("ydbl_nms", "ydbl_detect_topk")]
         for nd, (a, b) in zip(nds, self.bounds):
             nd.out, nd.out_count = det[a:b].data_ptr(), count[a:b].data_ptr()
 
@@ -729,6 +764,25 @@ class AugmentSession(DetectSession):
     def feats(self):
         """None: the reference's augmented forward returns (y, None) (U/nn/tasks.py:376)."""
         return None
+
+
+class E2EForwardSession(BatchSession):
+    """DetectionModel.forward on an end2end (YOLOv10) model: the forward with the head's whole inference forward
+    behind it (v10Detect._forward_plan: one2many and one2one branches, the one2one decode, the top-k with no
+    threshold and no clipping), one plan, one graph.  outputs(): (y [B, min(300, A), 6], {"one2many": [...],
+    "one2one": [...]}) as fresh tensors of the session's dtype."""
+
+    def __init__(self, model, batch: int, h: int, w: int, dtype=torch.float16, device="cuda", use_graph=True):
+        super().__init__(model, batch, h, w, dtype, use_graph, device, 1)
+        self._build()
+
+    def _compile(self) -> Plan:
+        cm = self.compiled = self.model.compile(self.batch, self.h, self.w, self.dtype, device=self.device,
+                                                head_forward=True)
+        return cm.plan
+
+    def outputs(self):
+        return self.compiled.finish()
 
 
 class EmbedSession(BatchSession):

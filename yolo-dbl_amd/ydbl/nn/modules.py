@@ -23,6 +23,7 @@ U/nn/tasks.py:217) is folded into its pointwise conv here.
 
 from __future__ import annotations
 
+import copy
 import ctypes as C
 import math
 import os
@@ -437,8 +438,6 @@ class PlanModule(nn.Module):
 
 
 def _meta_copy(m: nn.Module) -> nn.Module:
-    import copy
-
     return copy.deepcopy(m).to("meta")
 
 
@@ -467,8 +466,6 @@ def emit_torch(m: nn.Module, plan: Plan, x, out: TV | None = None) -> TV:
     y = out if out is not None else plan.alloc(*shape)
     if y.shape != shape:
         raise ValueError(f"plugin {type(m).__name__}: output {shape} does not fit the destination {y.shape}")
-    import copy
-
     dm = copy.deepcopy(m).to(plan.device)
     if plan.device.type != "meta":
         dm = dm.to(plan.dtype)
@@ -903,6 +900,144 @@ class C2PSA(PlanModule):
         for i, m in enumerate(self.m):  # intermediate b's get buffers of their own
             b = m.emit(plan, b, buf.cslice(c, c) if i == n - 1 else None)
         return self.cv2.emit(plan, buf, out)
+
+
+class PSA(PlanModule):
+    """U/nn/modules/block.py:970-1010 (YOLOv10) — C2PSA's body for one block, written out: cv1 writes [a | b] into one
+    2c buffer, b + attn(b) and b + ffn(b) ride in proj's and ffn[1]'s epilogues, the last one back into the b slice,
+    cv2 reads the buffer.  num_heads = c // 64, so every stock scale meets Attention's head_dim 64 / key_dim 32."""
+
+    def __init__(self, c1, c2, e=0.5):
+        super().__init__()
+        assert c1 == c2
+        self.c = int(c1 * e)
+        self.cv1 = Conv(c1, 2 * self.c, 1, 1)
+        self.cv2 = Conv(2 * self.c, c1, 1)
+        self.attn = Attention(self.c, attn_ratio=0.5, num_heads=self.c // 64)
+        self.ffn = nn.Sequential(Conv(self.c, self.c * 2, 1), Conv(self.c * 2, self.c, 1, act=False))
+
+    def emit(self, plan, x, out=None):
+        c = self.c
+        buf = plan.alloc(x.n, x.h, x.w, 2 * c)
+        self.cv1.emit(plan, x, buf)
+        b = buf.cslice(c, c)
+        b1 = self.attn.emit(plan, b, None, res=b)
+        h = self.ffn[0].emit(plan, b1)
+        self.ffn[1].emit(plan, h, b, res=b1, res_mode=_lib.RES_ADD)  # (b's readers, qkv and proj, are behind us)
+        return self.cv2.emit(plan, buf, out)
+
+
+class SCDown(PlanModule):
+    """U/nn/modules/block.py:1088-1120 (YOLOv10) — Conv 1x1, then a depthwise k x k stride-s Conv without activation."""
+
+    def __init__(self, c1, c2, k, s):
+        super().__init__()
+        self.cv1 = Conv(c1, c2, 1, 1)
+        self.cv2 = Conv(c2, c2, k=k, s=s, g=c2, act=False)
+
+    def emit(self, plan, x, out=None):
+        return self.cv2.emit(plan, self.cv1.emit(plan, x), out)
+
+
+@torch.no_grad()
+def _fuse_conv_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d) -> nn.Conv2d:
+    """fuse_conv_and_bn (U/utils/torch_utils.py:238-265), its op sequence, as a new nn.Conv2d with a bias."""
+    fused = nn.Conv2d(conv.in_channels, conv.out_channels, conv.kernel_size, conv.stride, conv.padding,
+                      conv.dilation, conv.groups, bias=True).requires_grad_(False).to(conv.weight.device)
+    w_conv = conv.weight.view(conv.out_channels, -1)
+    w_bn = torch.diag(bn.weight.div(torch.sqrt(bn.eps + bn.running_var)))
+    fused.weight.copy_(torch.mm(w_bn, w_conv).view(fused.weight.shape))
+    b_conv = (torch.zeros(conv.weight.shape[0], device=conv.weight.device, dtype=conv.weight.dtype)
+              if conv.bias is None else conv.bias)
+    b_bn = bn.bias - bn.weight.mul(bn.running_mean).div(torch.sqrt(bn.running_var + bn.eps))
+    fused.bias.copy_(torch.mm(w_bn, b_conv.reshape(-1, 1)).reshape(-1) + b_bn)
+    return fused
+
+
+class RepVGGDW(PlanModule):
+    """U/nn/modules/block.py:756-815 (YOLOv10) — SiLU(dw7x7(x) + dw3x3(x)), both with BN, as ONE 7x7 depthwise launch:
+    the weights are folded when the plan is built exactly as fuse() folds them (BN into both, the 3x3 zero-padded to
+    7x7, weights and biases added).  fuse() -- the reference's, called by DetectionModel.fuse() -- leaves ``conv`` an
+    nn.Conv2d with a bias and no ``conv1``; both forms are accepted, and both load their own state_dict."""
+
+    def __init__(self, ed):
+        super().__init__()
+        self.conv = Conv(ed, ed, 7, 1, 3, g=ed, act=False)
+        self.conv1 = Conv(ed, ed, 3, 1, 1, g=ed, act=False)
+        self.dim = ed
+        self.act = nn.SiLU()
+
+    @property
+    def conv2d(self) -> nn.Conv2d:
+        """The 7x7 depthwise nn.Conv2d (its geometry is the launch's), fused or not."""
+        return self.conv.conv if isinstance(self.conv, Conv) else self.conv
+
+    @torch.no_grad()
+    def fuse(self):
+        """block.py:791-815."""
+        if not hasattr(self, "conv1"):
+            return
+        conv = _fuse_conv_bn(self.conv.conv, self.conv.bn)
+        conv1 = _fuse_conv_bn(self.conv1.conv, self.conv1.bn)
+        conv1_w = torch.nn.functional.pad(conv1.weight, [2, 2, 2, 2])
+        final_w, final_b = conv.weight + conv1_w, conv.bias + conv1.bias
+        conv.weight.data.copy_(final_w)
+        conv.bias.data.copy_(final_b)
+        self.conv = conv
+        del self.conv1
+
+    def folded(self):
+        """(w [c, 1, 7, 7], b [c]) fp32 on the host: fuse()'s arithmetic, the module left as it is."""
+        if not hasattr(self, "conv1"):
+            return self.conv.weight.detach().float().cpu(), self.conv.bias.detach().float().cpu()
+        (w7, b7), (w3, b3) = self.conv.folded(), self.conv1.folded()
+        return w7 + torch.nn.functional.pad(w3, [2, 2, 2, 2]), b7 + b3
+
+    def emit(self, plan, x, out=None, res=None, res_mode=_lib.RES_NONE):
+        w, b = self.folded()
+        return emit_conv2d(plan, self.conv2d, x, out, w, b, _act_code(self.act), res, res_mode, what="RepVGGDW.dw7")
+
+
+class _RepDW:
+    """What emit_dw_pw reads of a DWConv (conv, act, folded, emit), for a RepVGGDW."""
+
+    def __init__(self, m: RepVGGDW):
+        self.conv, self.act, self.folded, self.emit = m.conv2d, m.act, m.folded, m.emit
+
+
+class CIB(PlanModule):
+    """U/nn/modules/block.py:818-850 (YOLOv10) — dw3 -> pw -> dw3 (lk: RepVGGDW) -> pw -> dw3 [+ x].  The two
+    depthwise -> pointwise pairs go through emit_dw_pw (one launch each where the fused DSConv kernel takes the
+    shape, else two); the shortcut rides in the last depthwise conv's epilogue."""
+
+    def __init__(self, c1, c2, shortcut=True, e=0.5, lk=False):
+        super().__init__()
+        c_ = int(c2 * e)
+        self.cv1 = nn.Sequential(
+            Conv(c1, c1, 3, g=c1),
+            Conv(c1, 2 * c_, 1),
+            RepVGGDW(2 * c_) if lk else Conv(2 * c_, 2 * c_, 3, g=2 * c_),
+            Conv(2 * c_, c2, 1),
+            Conv(c2, c2, 3, g=c2),
+        )
+        self.add = shortcut and c1 == c2
+
+    def emit(self, plan, x, out=None):
+        m = self.cv1
+        t, _ = emit_dw_pw(plan, m[0], m[1], x, what="CIB.dw+pw")
+        dw = _RepDW(m[2]) if isinstance(m[2], RepVGGDW) else m[2]
+        t, _ = emit_dw_pw(plan, dw, m[3], t, what="CIB.dw+pw")
+        return m[4].emit(plan, t, out, res=x if self.add else None,
+                         res_mode=_lib.RES_ADD if self.add else _lib.RES_NONE)
+
+
+class C2fCIB(C2f):
+    """U/nn/modules/block.py:853-880 (YOLOv10) — C2f whose blocks are CIBs; they chain through the slices of the concat
+    buffer (C2f.emit)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=False, lk=False, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.m = nn.ModuleList(CIB(self.c, self.c, shortcut, e=1.0, lk=lk) for _ in range(n))
 
 
 class AAttn(PlanModule):
@@ -1439,28 +1574,129 @@ class Detect(PlanModule):
         """Per level: one NHWC buffer [B,h,w,64+nc] (box logits | class logits) = the reference's x[i].  Box branch
         first; a DetectSession on the sparse box path moves the one-launch box branch of a level behind the level's
         class tail once it knows its thresholds (engine.session.DetectSession._sparse_box)."""
+        return self._emit_branches(plan, xs, self.cv2, self.cv3)
+
+    def _emit_branches(self, plan, xs, cv2, cv3):
+        """emit() for one set of box / class branches (an end2end head has two)."""
         levels = []
         for i, x in enumerate(xs):
             lv = plan.alloc(x.n, x.h, x.w, self.no)
-            if not emit_detect_box(plan, self.cv2[i], x, lv.cslice(0, 4 * self.reg_max)):
-                t = emit_conv3x3_pair(plan, self.cv2[i][0], self.cv2[i][1], x)
-                emit_conv2d(plan, self.cv2[i][2], t, lv.cslice(0, 4 * self.reg_max), what="Detect.box")
+            if not emit_detect_box(plan, cv2[i], x, lv.cslice(0, 4 * self.reg_max)):
+                t = emit_conv3x3_pair(plan, cv2[i][0], cv2[i][1], x)
+                emit_conv2d(plan, cv2[i][2], t, lv.cslice(0, 4 * self.reg_max), what="Detect.box")
             if self.legacy:
-                u = self.cv3[i][0].emit(plan, x)
-                u = self.cv3[i][1].emit(plan, u)
+                u = cv3[i][0].emit(plan, x)
+                u = cv3[i][1].emit(plan, u)
             else:  # [DWConv, Conv1x1] x 2: each pair is one fused depthwise -> pointwise launch; the class conv
                 # cv3[i][2] (64 -> nc <= 4) rides in the second pair's epilogue, and the pair's own 64-channel
                 # output then has no reader (only the class logits leave the launch: y_unused)
                 cls_out = lv.cslice(4 * self.reg_max, self.nc)
-                u, _ = emit_dw_pw(plan, self.cv3[i][0][0], self.cv3[i][0][1], x)
-                u, done = emit_dw_pw(plan, self.cv3[i][1][0], self.cv3[i][1][1], u, tail_conv=self.cv3[i][2],
+                u, _ = emit_dw_pw(plan, cv3[i][0][0], cv3[i][0][1], x)
+                u, done = emit_dw_pw(plan, cv3[i][1][0], cv3[i][1][1], u, tail_conv=cv3[i][2],
                                      tail_out=cls_out, y_unused=True)
                 if done:
                     levels.append(lv)
                     continue
-            emit_conv2d(plan, self.cv3[i][2], u, lv.cslice(4 * self.reg_max, self.nc), what="Detect.cls")
+            emit_conv2d(plan, cv3[i][2], u, lv.cslice(4 * self.reg_max, self.nc), what="Detect.cls")
             levels.append(lv)
         return levels
+
+
+class v10Detect(Detect):  # noqa: N801 (reference name)
+    """U/nn/modules/head.py:768-817 (YOLOv10) on Detect.forward_end2end (:120-141) — end2end = True: the class branch is
+    Conv(x, x, 3, g=x) -> Conv1x1 (the DWConv pair written as grouped Convs), and one2one_cv2 / one2one_cv3 are deep
+    copies of both branch sets.  Inference decodes the ONE2ONE maps, with xyxy boxes (ydbl_detect_decode_e2e), and
+    selects with a top-k instead of an NMS (ydbl_detect_topk); max_det = 300 is the head's own, never the
+    predictor's.  emit() in a session runs only the one2one branches: the one2many maps have no reader at
+    inference.  forward(x) returns the reference's (y [B, min(300, A), 6], {"one2many": [...], "one2one": [...]})."""
+
+    end2end = True
+    max_det = 300
+
+    def __init__(self, nc: int = 80, ch: tuple = ()):
+        super().__init__(nc, ch)
+        self.legacy = False  # the class branch below is the DWConv -> Conv1x1 form whatever the model's flag
+        c3 = max(ch[0], min(self.nc, 100))
+        self.cv3 = nn.ModuleList(
+            nn.Sequential(
+                nn.Sequential(Conv(x, x, 3, g=x), Conv(x, c3, 1)),
+                nn.Sequential(Conv(c3, c3, 3, g=c3), Conv(c3, c3, 1)),
+                nn.Conv2d(c3, self.nc, 1),
+            )
+            for x in ch
+        )
+        self.one2one_cv2 = copy.deepcopy(self.cv2)
+        self.one2one_cv3 = copy.deepcopy(self.cv3)
+
+    def bias_init(self):
+        """U/nn/modules/head.py:183-194: both branch sets."""
+        super().bias_init()
+        for a, b, s in zip(self.one2one_cv2, self.one2one_cv3, self.stride):
+            a[-1].bias.data[:] = 1.0
+            b[-1].bias.data[: self.nc] = math.log(5 / self.nc / (640 / s) ** 2)
+
+    def emit(self, plan, xs, out=None):
+        return self._emit_branches(plan, xs, self.one2one_cv2, self.one2one_cv3)
+
+    def _forward_plan(self, plan, xs):
+        """forward(x) in inference mode (head.py:120-141 with export False): both branch sets, the one2one maps
+        decoded to xyxy (ydbl_detect_decode_e2e) and Detect.postprocess (head.py:200-221) as ydbl_detect_topk with no
+        score threshold, no clipping and k = min(max_det, A).  Returns the call's finisher ->
+        (y [B, k, 6], {"one2many": [x_i], "one2one": [x_i]}) as fresh tensors of the plan's dtype."""
+        if not float(self.stride.abs().sum()):
+            raise RuntimeError("Detect.stride is unset: build the module through DetectionModel (stride probe)")
+        many = self._emit_branches(plan, xs, self.cv2, self.cv3)
+        one = self.emit(plan, xs)
+        B = one[0].n
+        A = sum(lv.h * lv.w for lv in one)
+        tail = E2ETail(plan, one, self.stride.tolist(), self.nc, B, conf=-1.0, k_head=min(self.max_det, A),
+                       max_det=min(self.max_det, A))
+        dt = plan.dtype
+        return lambda: (tail.det.to(dt, copy=True), {"one2many": [lv.nchw().contiguous() for lv in many],
+                                                     "one2one": [lv.nchw().contiguous() for lv in one]})
+
+
+class E2ETail:
+    """The detection tail of an end2end head behind its one2one levels, appended to `plan`: ydbl_detect_decode_e2e in
+    multi-label mode (cap = A * nc candidates per image, xyxy boxes, no `classes` filter: that one follows the cut)
+    and ydbl_detect_topk into det [B, max_det, 6] / count [B].  conf: the candidates' threshold (score > conf; -1 =
+    every pair, DetectionModel.forward); k_head = min(the head's max_det, A); det / count / pred: the caller's
+    buffers (views with their own image stride are fine), else allocated; classes: a device int32 tensor or None;
+    clip = (h, w) or None; per_image: ydbl_topk_desc's schedule; topk=False: the decode alone."""
+
+    def __init__(self, plan: Plan, levels, strides, nc, batch, conf, k_head, max_det, det=None, count=None, pred=None,
+                 classes=None, clip=None, per_image=False, topk=True):
+        dev = plan.device
+        A = sum(lv.h * lv.w for lv in levels)
+        cap = self.cap = A * nc
+        self.cand_box = torch.empty((batch, cap, 4), dtype=torch.float32, device=dev)
+        self.cand_score = torch.empty((batch, cap), dtype=torch.float32, device=dev)
+        self.cand_cls = torch.empty((batch, cap), dtype=torch.int32, device=dev)
+        self.cand_idx = torch.empty((batch, cap), dtype=torch.int32, device=dev)
+        self.cand_count = torch.zeros((batch,), dtype=torch.int32, device=dev)
+        self.det = det if det is not None else torch.zeros((batch, max_det, 6), dtype=torch.float32, device=dev)
+        self.count = count if count is not None else torch.zeros((batch,), dtype=torch.int32, device=dev)
+        nws = 16 if dev.type == "meta" else int(_lib.lib.ydbl_detect_topk_workspace(batch, cap))
+        self.ws = torch.empty(nws, dtype=torch.uint8, device=dev)
+        plan.buffers += [self.cand_box, self.cand_score, self.cand_cls, self.cand_idx, self.cand_count, self.det,
+                         self.count, self.ws, *(t for t in (classes, pred) if t is not None)]
+        boxes = (View * 3)(*[lv.cslice(0, 64).struct() for lv in levels])
+        clss = (View * 3)(*[lv.cslice(64, nc).struct() for lv in levels])
+        st = (C.c_float * 3)(*[float(s) for s in strides])
+        self.dd = _lib.DecodeDesc(boxes, clss, len(levels), nc, st, float(conf), 1, None, 0,
+                                  pred.data_ptr() if pred is not None else None, self.cand_box.data_ptr(),
+                                  self.cand_score.data_ptr(), self.cand_cls.data_ptr(), self.cand_idx.data_ptr(),
+                                  self.cand_count.data_ptr(), cap)
+        plan.launch("ydbl_detect_decode_e2e", self.dd, what="Detect.decode e2e", keep=[self.dd])
+        if not topk:
+            return
+        self.td = _lib.TopkDesc(self.cand_box.data_ptr(), self.cand_score.data_ptr(), self.cand_cls.data_ptr(),
+                                self.cand_idx.data_ptr(), self.cand_count.data_ptr(), batch, cap, int(k_head),
+                                int(max_det), classes.data_ptr() if classes is not None else None,
+                                len(classes) if classes is not None else 0, float(clip[1]) if clip else 0.0,
+                                float(clip[0]) if clip else 0.0, self.det.data_ptr(), self.count.data_ptr(),
+                                self.det.stride(0), self.count.stride(0), self.ws.data_ptr(), nws, int(bool(per_image)))
+        plan.launch("ydbl_detect_topk", self.td, what="TopK", keep=[self.td])
 
 
 def emit_module(m: nn.Module, plan: Plan, x, out=None):

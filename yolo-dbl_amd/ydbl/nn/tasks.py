@@ -38,12 +38,13 @@ REGISTRY: dict[str, type] = {
     for c in (M.Conv, M.DWConv, M.DSConv, M.GhostConv, M.Concat, M.Bottleneck, M.C2f, M.C3, M.C3Ghost,
               M.GhostBottleneck, M.DSBottleneck, M.DSC3k, M.DSC3k2, M.HyperACE, M.DownsampleConv,
               M.FullPAD_Tunnel, M.DySample, M.LSKblock, M.Detect, M.AAttn, M.ABlock, M.A2C2f, M.SPPF, M.C3k, M.C3k2,
-              M.Attention, M.PSABlock, M.C2PSA)
+              M.Attention, M.PSABlock, M.C2PSA, M.PSA, M.SCDown, M.RepVGGDW, M.CIB, M.C2fCIB, M.v10Detect)
 }
 REGISTRY["nn.Upsample"] = M.Upsample  # the one torch.nn layer name the v13 YAMLs use (U/nn/tasks.py:972-973)
 _C1C2 = {"Conv", "DWConv", "GhostConv", "Bottleneck", "GhostBottleneck", "C2f", "C3", "C3Ghost", "DSC3k2", "DSConv",
-         "DSBottleneck", "A2C2f", "SPPF", "C3k2", "C2PSA"}
-_REPEAT_ARG = {"C2f", "C3", "C3Ghost", "DSC3k2", "A2C2f", "C3k2", "C2PSA"}
+         "DSBottleneck", "A2C2f", "SPPF", "C3k2", "C2PSA", "PSA", "SCDown", "C2fCIB"}
+_REPEAT_ARG = {"C2f", "C3", "C3Ghost", "DSC3k2", "A2C2f", "C3k2", "C2PSA", "C2fCIB"}
+_DETECT = {"Detect", "v10Detect"}  # U/nn/tasks.py:1107
 _C1_ONLY = {"DySample", "LSKblock"}
 
 
@@ -169,7 +170,7 @@ def parse_model(d: dict, ch: int = 3, verbose: bool = False):
                     args += [True, 1.5]
         elif name == "Concat":
             c2 = sum(ch[x] for x in f)
-        elif name == "Detect":
+        elif name in _DETECT:
             args.append([ch[x] for x in f])
         elif name == "HyperACE":
             legacy = False
@@ -197,6 +198,8 @@ def parse_model(d: dict, ch: int = 3, verbose: bool = False):
             m.legacy = legacy  # class attribute, as the reference sets it (U/nn/tasks.py:1111-1112)
             m_ = m(*args)
             m_.legacy = legacy  # and on the instance: a yolov8 (legacy) and a yolo11 model may live in one process
+        elif name == "v10Detect":  # builds its own class branch: Detect's class attribute is left as it is
+            m_ = m(*args)
         else:
             m_ = nn.Sequential(*(m(*args) for _ in range(n))) if n > 1 else m(*args)
         m_.np = sum(x.numel() for x in m_.parameters())
@@ -223,8 +226,8 @@ class DetectionModel(nn.Module):
         self.model, self.save = parse_model(deepcopy(self.yaml), ch=ch, verbose=verbose)
         self.names = {i: f"{i}" for i in range(self.yaml["nc"])}
         self.inplace = self.yaml.get("inplace", True)
-        self.end2end = False
         m = self.model[-1]
+        self.end2end = bool(getattr(m, "end2end", False))  # U/nn/tasks.py:331
         # Stride probe by shape propagation at 256x256 (the reference runs a train-mode forward on
         # zeros, U/nn/tasks.py:337-350; only its output shapes are used for the strides).
         s = 256
@@ -280,6 +283,13 @@ class DetectionModel(nn.Module):
             raise ValueError(f"input has {x.shape[1]} channels, the model {self.yaml['ch']}")
         if embed:  # _predict_once's early return (U/nn/tasks.py:168-171): torch.unbind(torch.cat(embeddings, 1), 0)
             return self._run(x, embed=embed)[1].to(x.dtype, copy=True).unbind(0)
+        if self.end2end:
+            # an end2end head (v10Detect.forward_end2end, U/nn/modules/head.py:120-141): (y [B, min(300, A), 6],
+            # {"one2many", "one2one"}) from the head's own forward on the neck's maps -- Detect.postprocess as a top-k
+            # with no threshold and no clipping.  _predict_augment (U/nn/tasks.py:361-366) warns and runs this pass
+            if augment:
+                warn_e2e_augment()
+            return self._run(x, e2e=True)[1]
         s, _ = self._run(x, augment=augment)
         y = s.pred.to(x.dtype, copy=True)
         if augment:
@@ -293,6 +303,7 @@ class DetectionModel(nn.Module):
         """U/nn/tasks.py:358-359 (DetectionModel.init_criterion)."""
         from ..utils.loss import v8DetectionLoss
 
+        check_e2e_loss(self)
         return v8DetectionLoss(self, max_labels=self.MAX_LABELS)
 
     def loss(self, batch, preds=None):
@@ -303,6 +314,7 @@ class DetectionModel(nn.Module):
         (MAX_LABELS per image) refilled before the replay, like the input.  An image with more labels, or a class
         outside [0, nc), raises ValueError on the host before anything is launched.  preds given (the ``feats`` list
         or the ``(y, feats)`` tuple of forward): the criterion alone (utils.loss.v8DetectionLoss)."""
+        check_e2e_loss(self)
         if getattr(self, "criterion", None) is None:
             self.criterion = self.init_criterion()
         if preds is not None:
@@ -338,14 +350,15 @@ class DetectionModel(nn.Module):
                 break
         return s, out
 
-    def _forward_session(self, b, h, w, half, device, fresh=None, augment=False, embed=None, loss=False):
-        from ..engine.session import AugmentSession, DetectOptions, DetectSession, EmbedSession, default_streams
+    def _forward_session(self, b, h, w, half, device, fresh=None, augment=False, embed=None, loss=False, e2e=False):
+        from ..engine.session import (AugmentSession, DetectOptions, DetectSession, E2EForwardSession, EmbedSession,
+                                      default_streams)
 
         cache = self.__dict__.setdefault("_fwd_sessions", {})
         # compiled plans hold the routing of the YDBL_* switches at build time (part of the key) and BN-folded
         # copies of the weights (the session's wsig, checked by forward() after each launch)
         key = ((b, h, w, half, str(device), ydbl_env(), augment) + ((embed,) if embed else ())
-               + ((("loss", self.MAX_LABELS),) if loss else ()))
+               + ((("loss", self.MAX_LABELS),) if loss else ()) + (("e2e",) if e2e else ()))
         s = cache.pop(key, None)
         if s is not None and fresh is not None and s.wsig != fresh:
             s = None  # weights changed since this plan was built
@@ -356,6 +369,8 @@ class DetectionModel(nn.Module):
             with torch.cuda.device(device):
                 if embed:
                     s = EmbedSession(self, b, h, w, dtype, embed, device=device, streams=default_streams(b))
+                elif e2e:
+                    s = E2EForwardSession(self, b, h, w, dtype, device=device)
                 else:  # forward + decode, no NMS; loss: + ydbl_detect_loss on dense levels, one plan (a loss session
                     # never splits: one normaliser for the batch)
                     opt = DetectOptions(dtype, keep_pred=True, nms=False,
@@ -377,7 +392,13 @@ class DetectionModel(nn.Module):
         return super().load_state_dict(*args, **kwargs)
 
     def fuse(self, verbose=False):
-        """BN folding happens when a plan is compiled (exactly fuse_conv_and_bn's arithmetic); kept for API parity."""
+        """BaseModel.fuse (U/nn/tasks.py:207-235).  Conv's BN folding happens when a plan is compiled (exactly
+        fuse_conv_and_bn's arithmetic); a RepVGGDW is folded here as the reference folds it (block.py:791-815: both
+        branches' BN, the 3x3 padded into the 7x7, one nn.Conv2d left), which the plan then takes as it is."""
+        for m in self.modules():
+            if isinstance(m, M.RepVGGDW):
+                m.fuse()
+        self.invalidate()
         self._fused = True
         return self
 
@@ -385,7 +406,7 @@ class DetectionModel(nn.Module):
         return self._fused
 
     def compile(self, batch: int, h: int, w: int, dtype=torch.float16, device="cuda", bind=None, embed=None,
-                embed_out=None) -> "CompiledModel":
+                embed_out=None, head_forward=False) -> "CompiledModel":
         """Build the launch plan of one forward: input NCHW fp32 [batch,3,h,w] -> per-level head outputs.
         The plan reads its batch through an input binding (include/ydbl.h ydbl_input_bind): bind_ptr, a device int64
         holding the batch pointer (initially the plan's own staging buffer ``input``), and bind_amax, a device fp32
@@ -396,7 +417,11 @@ class DetectionModel(nn.Module):
         (U/nn/tasks.py:158-171).  Layers 0..max(embed) only -- no head, no concat buffer past the cut (a producer whose
         concat lies past it writes a buffer of its own) -- and right behind the launches of each named layer one
         ydbl_global_avgpool ("embed.pool") of its output into its columns of ``embed_out`` [batch, sum C_i] (plan
-        dtype; a caller's 2-D view with its own row stride for a split session).  The result has levels = None."""
+        dtype; a caller's 2-D view with its own row stride for a split session).  The result has levels = None.
+
+        head_forward (an end2end head): the head's whole inference forward (v10Detect._forward_plan: both branch sets,
+        decode, top-k) in place of its emit; the result has levels = None and ``finish`` = the call that returns the
+        forward's outputs as fresh tensors."""
         plan = Plan(torch.device(device), dtype)
         if embed is not None:
             embed = normalize_embed(embed, len(self.model))
@@ -485,13 +510,18 @@ class DetectionModel(nn.Module):
                 if m.f != -1:
                     x = y[m.f] if isinstance(m.f, int) else [x if j == -1 else y[j] for j in m.f]
                 out = cat_buf.get(m.i, out_hint.get(m.i))
-                x = M.emit_module(m, plan, x, out)
+                if head_forward and m is layers[-1]:
+                    finish, x = m._forward_plan(plan, x), None
+                else:
+                    x = M.emit_module(m, plan, x, out)
                 y.append(x)
             if pool is not None:
                 pool(m.i, x)
         cm = CompiledModel(plan, x_nchw, inp, x if embed is None else None, self.model[-1])
         if embed is not None:
             cm.embed, cm.embed_out, cm.embed_views = embed, embed_out, views
+        if head_forward:
+            cm.finish = finish
         cm.bind_ptr, cm.bind_amax = bind_ptr, bind_amax
         # the InputBind records the launches read (retargeted by CompiledModel.set_bind)
         cm.bind_holders = [st.args[0].bind if st.fn.__name__ == "ydbl_conv_stem2" else st.args[-1]
@@ -499,6 +529,28 @@ class DetectionModel(nn.Module):
                                                                        "ydbl_input_nchw_to_nhwc")]
         cm.set_bind(None)  # the plan's own staging buffer, read directly (DetectSession slot 0)
         return cm
+
+
+_E2E_AUGMENT_WARNED = False
+
+
+def warn_e2e_augment():
+    """_predict_augment on an end2end model (U/nn/tasks.py:361-366): a warning, once, and the plain pass."""
+    global _E2E_AUGMENT_WARNED
+    if not _E2E_AUGMENT_WARNED:
+        import warnings
+
+        warnings.warn("End2End model does not support 'augment=True' prediction. Reverting to single-scale "
+                      "prediction.", stacklevel=3)
+        _E2E_AUGMENT_WARNED = True
+
+
+def check_e2e_loss(model):
+    """The criterion of an end2end model is E2EDetectLoss (U/utils/loss.py:728-743), the dual-assignment loss over
+    both branch sets: not implemented.  Raised on the host, before any device work."""
+    if getattr(model, "end2end", False):
+        raise NotImplementedError("the loss of an end2end (YOLOv10) model is E2EDetectLoss (one2many + one2one "
+                                  "assignment), which is not implemented")
 
 
 class CompiledModel:
@@ -547,8 +599,16 @@ def _propagate_shapes(layers, batch, h, w, ch):
         elif t in ("Bottleneck", "DSBottleneck"):
             cur = (batch, src[1], src[2], (m[-1] if isinstance(m, nn.Sequential) else m).cv2.conv.out_channels
                    if t == "Bottleneck" else (m[-1] if isinstance(m, nn.Sequential) else m).cv2.pw.out_channels)
-        elif t in ("C2f", "DSC3k2", "A2C2f", "C3k2", "SPPF", "C2PSA"):
+        elif t in ("C2f", "DSC3k2", "A2C2f", "C3k2", "SPPF", "C2PSA", "PSA", "C2fCIB"):
             cur = (batch, src[1], src[2], mm.cv2.conv.out_channels)
+        elif t == "SCDown":
+            c = mm.cv2.conv
+            cur = (batch, *M.conv_out_hw(src[1], src[2], c.kernel_size[0], c.stride[0], c.padding[0], c.dilation[0]),
+                   c.out_channels)
+        elif t == "CIB":
+            cur = (batch, src[1], src[2], (m[-1] if isinstance(m, nn.Sequential) else m).cv1[4].conv.out_channels)
+        elif t == "RepVGGDW":
+            cur = src
         elif t in ("AAttn", "ABlock", "Attention", "PSABlock"):
             cur = src
         elif t == "nn.Upsample":
@@ -568,7 +628,7 @@ def _propagate_shapes(layers, batch, h, w, ch):
             cur = src[0]
         elif t == "Concat":
             cur = (batch, src[0][1], src[0][2], sum(s_[3] for s_ in src))
-        elif t == "Detect":
+        elif t in _DETECT:
             cur = None
         elif not hasattr(mm, "emit"):  # a registered forward-only plugin: its output shape from a meta run
             cur = M.torch_out_shape(m, src)

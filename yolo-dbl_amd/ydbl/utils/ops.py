@@ -72,6 +72,15 @@ def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=Non
         prediction = prediction[0]
     if rotated or (labels is not None and len(labels)):
         raise NotImplementedError("rotated / autolabel NMS is not on the YOLO-DBL path")
+    if prediction.shape[-1] == 6:
+        # an end2end model's output [B, N, 6] (U/utils/ops.py:224-228): rows already selected and ordered by the head's
+        # top-k, so only the threshold, the cut and the class filter remain -- the reference's three lines, on whatever
+        # device the rows are (the sessions do this step inside ydbl_detect_topk; nothing here is a hot path)
+        output = [pred[pred[:, 4] > conf_thres][:max_det] for pred in prediction]
+        if classes is not None:
+            cls_t = torch.tensor(list(classes), device=prediction.device)
+            output = [pred[(pred[:, 5:6] == cls_t).any(1)] for pred in output]
+        return output
     if not prediction.is_cuda:
         raise RuntimeError("ydbl non_max_suppression runs on the GPU only (prediction must be a CUDA tensor)")
     bs = prediction.shape[0]
