@@ -61,6 +61,11 @@
  *   ydbl_nms               <- utils/ops.py:278-310 (+ torchvision.ops.nms, torchvision 0.23.0),
  *                             with clip_boxes utils/ops.py:319-338 as reached through
  *                             scale_boxes :92-127 for tensor sources (gain 1, pad 0)
+ *   ydbl_nms (out_idx)     <- the row index `i` of utils/ops.py:300-310 (output[xi] = x[i]): which prediction row a kept
+ *                             detection came from, so that its mask coefficients can be found afterwards
+ *   ydbl_deconv2x2_nhwc    <- nn.ConvTranspose2d(c_, c_, 2, 2, 0, bias=True) in Proto, nn/modules/block.py:87-104
+ *   ydbl_process_mask      <- process_mask / process_mask_native utils/ops.py:661-713 with crop_mask :644-658 and
+ *                             scale_masks :716-737 (F.interpolate bilinear, align_corners=False)
  *   ydbl_match_predictions <- DetectionValidator._process_batch models/yolo/detect/val.py:209-227
  *                             (box_iou utils/metrics.py:52-71 + BaseValidator.match_predictions
  *                             engine/validator.py:222-262, non-scipy branch)
@@ -521,6 +526,10 @@ typedef struct {
   void* workspace;
   int64_t out_stride, count_stride;
   int32_t per_image;
+  /* optional int32 [n][max_det] (image stride max_det), NULL = not written: row k of image b receives the kept
+   * candidate's cand_idx (anchor, or anchor * nc + cls in multi-label mode, as the decode wrote it), rows past the
+   * count -1 -- what finds a detection's mask coefficients after the NMS (ydbl_process_mask) */
+  int32_t* out_idx;
 } ydbl_nms_desc;
 int64_t ydbl_nms_workspace(int32_t n, int32_t cap, int32_t max_nms);
 int ydbl_nms(const ydbl_nms_desc* d, void* stream);
@@ -921,6 +930,68 @@ typedef struct {
   ydbl_view gbox[3], gcls[3];
 } ydbl_loss_grad_desc;
 int ydbl_detect_loss_grad(const ydbl_loss_grad_desc* d, void* stream);
+
+/* ConvTranspose2d(cin, cout, kernel 2, stride 2, pad 0) + bias + activation on NHWC views, one launch:
+ *   y[n][2i+dy][2j+dx][co] = act(bias[co] + sum_ci x[n][i][j][ci] * W[ci][co][dy][dx]).
+ * A GEMM with M = n*h*w, N = 4*cout, K = cin on MFMA (f16: 16x16x32, f32: exact 16x16x4, fp32 accumulation) whose four
+ * N-quarters are stored to the four (dy, dx) output pixels straight from the accumulators.
+ * x: [n,h,w,cin], y: [n,2h,2w,cout], the same dtype, 16-byte aligned channel vectors, any channel stride (lanes
+ * between c and cs are not touched); y must not overlap x.  cin and cout multiples of 32, else YDBL_EINVAL.
+ * w: packed on the host, [2*dy+dx][cout][cin] in the view dtype (torch's [cin][cout][2][2] permuted (2, 3, 1, 0)),
+ * 16-byte aligned.  bias: fp32 [cout], 16-byte aligned, or NULL.  act: a YDBL_ACT_* code. */
+typedef struct {
+  ydbl_view x, y;
+  const void* w;
+  const float* bias;
+  int32_t act;
+} ydbl_deconv_desc;
+int ydbl_deconv2x2_nhwc(const ydbl_deconv_desc* d, void* stream);
+
+/* Instance masks (process_mask / process_mask_native, U/utils/ops.py:644-737), one launch for a batch.
+ * For image b and slot k < min(count[b], max_det), with coefficients c (below) and the box
+ * (x1, y1, x2, y2) = (det[0] * sx, det[1] * sy, det[2] * sx, det[3] * sy) of row k (fp32 products):
+ *   m[r][q] = sum_j c[j] * float(proto[b][r][q][j])        fp32, over the proto grid
+ *   crop_after = 0: m is zeroed where not (q >= x1 && q < x2 && r >= y1 && r < y2) (float compares on the proto grid's
+ *     own indices), the window rows top..bottom-1, columns left..right-1 of it are resampled to (out_h, out_w)
+ *     bilinearly (torch's upsample_bilinear2d, align_corners=False: scale = float(in) / out,
+ *     src = max(scale * (d + 0.5) - 0.5, 0), i0 = int(src), i1 = min(i0 + 1, in - 1)), and the output is v > 0
+ *     -- process_mask with sx = fp32(mw / iw), sy = fp32(mh / ih) and the whole grid as the window; out_h, out_w equal
+ *     to the window is upsample=False (the resampling is then the identity);
+ *   crop_after = 1: the window is resampled first, the indicator is applied on the OUTPUT grid's indices, then > 0
+ *     -- process_mask_native with sx = sy = 1 and scale_masks' window.
+ * The plane of (b, k) is out + (row_offset[b] + k) * out_h * out_w elements, fp32 0 / 1 (YDBL_MASK_F32, the
+ * reference's) or uint8 0 / 1 (YDBL_MASK_U8); slots at or past the count write nothing.
+ * Coefficients: coef != NULL: fp32 [n][max_det][nm] given directly (mc, keep_idx unused).  Otherwise keep_idx
+ * int32 [n][max_det] (ydbl_nms's out_idx) names the anchor -- keep_idx itself when nc == 0, keep_idx / nc for the
+ * multi-label index anchor * nc + cls -- and the coefficients are that anchor's nm values of the level maps
+ * mc[0..nl) ([n,h_l,w_l,nm] views, f16 or f32, anchors counted level after level, row-major); an index outside the
+ * levels gives zero coefficients (an all-zero mask).
+ * proto: [n,mh,mw,nm] view, f16 or f32, 16-byte aligned channel vectors; nm a multiple of 8, <= 64.
+ * det: fp32 rows of det_row floats (0 = 6) whose first four are the box, det_stride floats between images
+ * (0 = max_det * det_row).  row_offset: int64 [n] on the device.  1 <= max_det <= 4096.  slots: the slot extent of
+ * the grid, 0 = max_det; a caller that knows max(count) passes it to launch no idle workgroups (slots past it are
+ * not written).  No atomics, every element of a live slot written once: bit-identical from run to run.  One launch
+ * on `stream`, no allocation, no sync. */
+enum { YDBL_MASK_F32 = 0, YDBL_MASK_U8 = 1 };
+typedef struct {
+  ydbl_view proto;
+  ydbl_view mc[3];
+  int32_t nl, nc;
+  const int32_t* keep_idx;
+  const float* det;
+  int64_t det_stride;
+  int32_t det_row, max_det;
+  const int32_t* count;
+  const float* coef;
+  const int64_t* row_offset;
+  void* out;
+  int32_t out_h, out_w, out_dtype;
+  int32_t top, left, bottom, right;
+  float sx, sy;
+  int32_t crop_after;
+  int32_t slots;
+} ydbl_mask_desc;
+int ydbl_process_mask(const ydbl_mask_desc* d, void* stream);
 
 const char* ydbl_last_error(void);
 const char* ydbl_version(void);

@@ -75,8 +75,16 @@ def _value(v, tp, base=None):
     return v
 
 
+# Optional descriptor fields appended to the C ABI after the fingerprint was recorded, each documented as "NULL =
+# the behaviour before the field existed": left out of a record while unset, so that the recorded plans stay
+# comparable; a session that sets one (a segmentation model's NMS writes out_idx) shows it.
+APPENDED = {"NmsDesc": ("out_idx",)}
+
+
 def _struct(d, rel):
-    return {name: _value(getattr(d, name), tp, rel.get(name)) for name, tp in d._fields_}
+    late = APPENDED.get(type(d).__name__, ())
+    return {name: _value(getattr(d, name), tp, rel.get(name)) for name, tp in d._fields_
+            if not (name in late and not getattr(d, name))}
 
 
 def plan_fingerprint(plan, top, own) -> list:

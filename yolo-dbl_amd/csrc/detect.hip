@@ -220,6 +220,7 @@ struct NmsArgs {
   float clip_w, clip_h;
   float* out; int* out_count;
   int64_t ostride; int64_t cstride;  // floats per image of out, int32s per image of out_count
+  int* out_idx;  // optional [n][max_det]: the kept rows' cand_idx, -1 past the count
 };
 
 // bitonic sort of P (power of two) key/value pairs; keys/vals in LDS or global, one workgroup
@@ -1120,10 +1121,13 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(NmsArgs p) {
     dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3];
     dst[4] = p.cscore[o];
     dst[5] = float(p.ccls[o]);
+    if (p.out_idx) p.out_idx[(int64_t)b * p.max_det + k] = p.cidx[o];
   }
   // rows kept..max_det of the fixed-shape output are zeroed (the all-gather ships whole buffers)
   float* rest = p.out + (int64_t)b * p.ostride + (int64_t)kept * 6;
   for (int k = threadIdx.x; k < (p.max_det - kept) * 6; k += NMS_THREADS) rest[k] = 0.f;
+  if (p.out_idx)
+    for (int k = kept + threadIdx.x; k < p.max_det; k += NMS_THREADS) p.out_idx[(int64_t)b * p.max_det + k] = -1;
   if (threadIdx.x == 0) p.out_count[(int64_t)b * p.cstride] = kept;
 }
 
@@ -1190,10 +1194,13 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_merge_kernel(NmsArgs p) {
     dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3];
     dst[4] = p.cscore[o];
     dst[5] = float(p.ccls[o]);
+    if (p.out_idx) p.out_idx[(int64_t)b * p.max_det + rank] = p.cidx[o];
   }
   const int kept = min(E, p.max_det);
   float* rest = p.out + (int64_t)b * p.ostride + (int64_t)kept * 6;
   for (int k = threadIdx.x; k < (p.max_det - kept) * 6; k += NMS_THREADS) rest[k] = 0.f;
+  if (p.out_idx)
+    for (int k = kept + threadIdx.x; k < p.max_det; k += NMS_THREADS) p.out_idx[(int64_t)b * p.max_det + k] = -1;
   if (threadIdx.x == 0) p.out_count[(int64_t)b * p.cstride] = kept;
 }
 
@@ -1362,6 +1369,7 @@ extern "C" int ydbl_nms(const ydbl_nms_desc* d, void* stream) {
   a.off_scale = d->agnostic ? 0.f : d->max_wh;
   a.clip_w = d->clip_w; a.clip_h = d->clip_h;
   a.out = d->out; a.out_count = d->out_count;
+  a.out_idx = d->out_idx;
   a.ostride = d->out_stride ? d->out_stride : (int64_t)d->max_det * 6;
   a.cstride = d->count_stride ? d->count_stride : 1;
   a.wrows = nms_rank_rows(d->cap);

@@ -107,7 +107,7 @@ class NmsDesc(C.Structure):
                 ("iou_thres", C.c_double), ("max_det", C.c_int32), ("max_nms", C.c_int32), ("agnostic", C.c_int32),
                 ("max_wh", C.c_float), ("clip_w", C.c_float), ("clip_h", C.c_float), ("out", C.c_void_p),
                 ("out_count", C.c_void_p), ("workspace", C.c_void_p), ("out_stride", C.c_int64),
-                ("count_stride", C.c_int64), ("per_image", C.c_int32)]
+                ("count_stride", C.c_int64), ("per_image", C.c_int32), ("out_idx", C.c_void_p)]
 
 
 class TopkDesc(C.Structure):
@@ -239,6 +239,24 @@ class LossGradDesc(C.Structure):
                 ("gbox", View * 3), ("gcls", View * 3)]
 
 
+class DeconvDesc(C.Structure):
+    """ydbl_deconv_desc: ConvTranspose2d(cin, cout, 2, 2) on NHWC views (Proto.upsample), packed weights."""
+    _fields_ = [("x", View), ("y", View), ("w", C.c_void_p), ("bias", C.c_void_p), ("act", C.c_int32)]
+
+
+MASK_F32, MASK_U8 = 0, 1
+
+
+class MaskDesc(C.Structure):
+    """ydbl_mask_desc: process_mask / process_mask_native for a batch, one launch."""
+    _fields_ = [("proto", View), ("mc", View * 3), ("nl", C.c_int32), ("nc", C.c_int32), ("keep_idx", C.c_void_p),
+                ("det", C.c_void_p), ("det_stride", C.c_int64), ("det_row", C.c_int32), ("max_det", C.c_int32),
+                ("count", C.c_void_p), ("coef", C.c_void_p), ("row_offset", C.c_void_p), ("out", C.c_void_p),
+                ("out_h", C.c_int32), ("out_w", C.c_int32), ("out_dtype", C.c_int32),
+                ("top", C.c_int32), ("left", C.c_int32), ("bottom", C.c_int32), ("right", C.c_int32),
+                ("sx", C.c_float), ("sy", C.c_float), ("crop_after", C.c_int32), ("slots", C.c_int32)]
+
+
 # name -> (argtypes, restype); every entry must exist in include/ydbl.h
 _P = C.c_void_p
 _VP = C.POINTER(View)
@@ -310,6 +328,8 @@ SIGNATURES = {
     "ydbl_detect_loss_workspace": ([C.c_int32, C.c_int32, C.c_int32], C.c_int64),
     "ydbl_detect_loss": ([C.POINTER(LossDesc), _P], C.c_int),
     "ydbl_detect_loss_grad": ([C.POINTER(LossGradDesc), _P], C.c_int),
+    "ydbl_deconv2x2_nhwc": ([C.POINTER(DeconvDesc), _P], C.c_int),
+    "ydbl_process_mask": ([C.POINTER(MaskDesc), _P], C.c_int),
     "ydbl_last_error": ([], C.c_char_p),
     "ydbl_version": ([], C.c_char_p),
 }

@@ -23,7 +23,7 @@ import torch
 
 from ..nn.tasks import DetectionModel, normalize_embed, weights_signature, ydbl_env
 from .results import Results
-from .session import AugmentSession, DetectOptions, DetectSession, EmbedSession, default_streams
+from .session import (AugmentSession, DetectOptions, DetectSession, EmbedSession, check_segment, default_streams)
 
 DEFAULTS = {"conf": 0.25, "iou": 0.7, "max_det": 300, "half": False, "fp8": False, "device": None, "agnostic_nms": False,
             "classes": None, "batch": 1, "verbose": False, "imgsz": 640,
@@ -34,7 +34,11 @@ DEFAULTS = {"conf": 0.25, "iou": 0.7, "max_det": 300, "half": False, "fp8": Fals
             # test-time augmentation (U/nn/tasks.py:361-398): three passes (1, 0.83 flipped, 0.67), one NMS
             "augment": False,
             # layer indices whose pooled outputs predict() returns instead of Results (U/cfg/default.yaml:67)
-            "embed": None}
+            "embed": None,
+            # segmentation models: masks at the original image's size, cropped after the resampling
+            # (process_mask_native, U/cfg/default.yaml:66); mask_dtype (ours): torch.uint8 keeps Masks.data as bytes
+            # instead of the reference's fp32 0 / 1
+            "retina_masks": False, "mask_dtype": None}
 
 
 def check_augment(augment, fp8=False, gather_rows=None) -> bool:
@@ -234,6 +238,8 @@ class Model:
             raise ValueError("build from a config and call .load(weights): YOLO('yolov13n_DBL.yaml').load('w.safetensors')")
         else:
             self.model = DetectionModel(model, nc=nc, verbose=verbose)
+        if self.model.segment:  # U/nn/tasks.py guess_model_task: a Segment head is the "segment" task
+            self.task = "segment"
         self.cfg = model
         self.overrides["model"] = model
 
@@ -305,6 +311,7 @@ class Model:
         gains): ydbl_detect_loss behind the head on dense levels, one plan for the whole batch (DetectSession.loss,
         load_labels)."""
         loss = check_loss(loss, augment, gather_rows)
+        check_segment(self.model, fp8, loss, gather_rows)  # before any device work
         if loss is not None:
             from ..nn.tasks import check_e2e_loss
 
@@ -318,6 +325,11 @@ class Model:
             from ..nn.tasks import warn_e2e_augment
 
             warn_e2e_augment()
+            augment = False
+        if augment and self.model.segment:  # the same rule: any class but DetectionModel
+            from ..nn.tasks import warn_no_augment
+
+            warn_no_augment()
             augment = False
         if loss is not None and embed is not None:
             raise ValueError("loss=True with embed: the truncated plan has no head to score")
@@ -401,6 +413,7 @@ class Model:
         args = {**DEFAULTS, **self.overrides, **kwargs}
         check_augment(args["augment"], args["fp8"])
         args["embed"] = check_embed(args["embed"], len(self.model.model), args["augment"], args["fp8"])
+        self._check_mask_args(args)
         dev = select_device(args["device"])
         t0 = time.perf_counter()
         if source is None:
@@ -442,7 +455,12 @@ class Model:
         # (_LazyCounts: one sync for the batch) -- on the copy path one device copy of det | count made now (the
         # session's buffers are reused by the next call); orig_img a view of the input batch (HWC, as LoadTensor
         # hands it over), made on first access.  speed["inference"] is the launch time.
-        if bo is not None:  # the slot's outputs, copied out of the slot on first access (or when it is reused)
+        mask_of = None
+        if self.model.segment:  # one host sync for the counts, then the masks from the plan's buffers in place
+            counts = cnt.tolist()
+            mask_of = self._masks(s, det, counts, args, [(h, w)] * b)
+            dets = det.clone()
+        elif bo is not None:  # the slot's outputs, copied out of the slot on first access (or when it is reused)
             dets, counts, scale = None, _LazyCounts(lambda: bo.detach().count), (lambda: bo.detach().scale[0])
         elif getattr(s, "out_flat", None) is not None:  # det | count: one copy
             flat = s.out_flat.clone()
@@ -458,8 +476,34 @@ class Model:
         else:
             box = lambda i: dets[i, : counts[i]]  # noqa: E731
         results = [Results(lambda i=i: hwc[i], path=f"image{i}.jpg", names=names, speed=speed, orig_shape=shape,
-                           boxes=lambda i=i: box(i)) for i in range(b)]
+                           boxes=lambda i=i: box(i), masks=(lambda i=i: mask_of(i)) if mask_of else None)
+                   for i in range(b)]
         return iter(results) if stream else results
+
+    def _check_mask_args(self, args):
+        """retina_masks / mask_dtype, on the host: mask_dtype must be torch.float32 (None) or torch.uint8; both mean
+        nothing to a model without a Segment head and are ignored there, as the reference ignores retina_masks."""
+        from ..utils.ops import mask_dtype_code
+
+        mask_dtype_code(args["mask_dtype"])
+        check_segment(self.model, args["fp8"])  # a segmentation model has no fp8 path: before the device lookup
+
+    @staticmethod
+    def _masks(s, det, counts, args, shapes, boxes=None):
+        """The masks of the batch session `s` just ran (SegmentationPredictor.postprocess,
+        U/models/yolo/segment/predict.py:48-58), launched now on the current stream, before `s` can run again.
+        counts: the host counts.  Default: process_mask(upsample=True) at the input size, one launch per sub-batch
+        plan into one [sum(counts), h, w] tensor.  retina_masks: process_mask_native at each image's own shape
+        (shapes[i]), one launch per image, with boxes[i] the image's kept rows already scaled to it (default: det's
+        rows as they are -- a tensor source, gain 1, pad 0).  -> i -> the image's [k, H, W] masks, or None when it has
+        no detection."""
+        dtype = args["mask_dtype"] or torch.float32
+        if not args["retina_masks"]:
+            allm, offs = s.masks(counts, dtype)
+            return lambda i: allm[offs[i]:offs[i + 1]] if counts[i] else None
+        per = [s.masks_native(i, boxes[i] if boxes is not None else det[i, : counts[i]], shapes[i], dtype)
+               if counts[i] else None for i in range(len(counts))]
+        return lambda i: per[i]
 
     def _embed_source(self, source, args, dev):
         """predict(embed=[...]): a generator of one 1-D tensor [D] per image in source order (the predictor yields
@@ -516,15 +560,18 @@ class Model:
         kw = self._session_kw(args, dev, clip=False)
         s = self.session(b, h, w, **kw)
         t1 = time.perf_counter()
-        _, (det, cnt) = self._launch(s, (b, h, w), kw, lambda s, _: s(im))
+        s, (det, cnt) = self._launch(s, (b, h, w), kw, lambda s, _: s(im))
         counts = cnt.tolist()
         t2 = time.perf_counter()
+        scaled = []
+        for i, f in enumerate(frames):
+            scaled.append(scale_boxes((h, w), det[i, : counts[i]].clone(), f.shape[:2]))
+        mask_of = (self._masks(s, det, counts, args, [f.shape[:2] for f in frames], scaled)
+                   if self.model.segment else None)
         results = []
         for i, f in enumerate(frames):
-            boxes = det[i, : counts[i]].clone()
-            scale_boxes((h, w), boxes, f.shape[:2])
             results.append(Results(f, path=paths[i] if paths else f"image{i}.jpg", names=self.model.names,
-                                   boxes=boxes))
+                                   boxes=scaled[i], masks=mask_of(i) if mask_of else None))
         t3 = time.perf_counter()
         speed = {"preprocess": (t1 - t0) * 1e3 / b, "inference": (t2 - t1) * 1e3 / b,
                  "postprocess": (t3 - t2) * 1e3 / b}
@@ -594,6 +641,7 @@ class Model:
         if max_tracks < 1:
             raise ValueError(f"max_tracks must be >= 1, got {max_tracks}")
         check_augment(args["augment"], args["fp8"])
+        self._check_mask_args(args)
         if source is None:
             raise ValueError("track() needs a source (no default asset is bundled)")
         is_tensor = isinstance(source, torch.Tensor) or (isinstance(source, (list, tuple)) and source
@@ -630,18 +678,22 @@ class Model:
         t1 = time.perf_counter()
         scale = _load_tensor_scale(im)
         # the session's copy path; the in-place binding is not needed here
-        _, (det, cnt) = self._launch(s, (b, h, w), kw, lambda s, _: s(im, scale))
+        s, (det, cnt) = self._launch(s, (b, h, w), kw, lambda s, _: s(im, scale))
         # the tracker reads the session's det | count in place, on the stream that wrote them; then one copy of them
         # for the images that keep their predicted boxes (the session's buffers are reused by the next call)
-        out, oc, tr = ts.update(det, cnt, [(h, w)] * b, reset_each=not persist)
+        seg = self.model.segment
+        out, oc, tr, *idx = ts.update(det, cnt, [(h, w)] * b, reset_each=not persist, want_idx=seg)
         dets, counts = det.clone(), cnt.clone()
+        lazy = LazyTracks(ts, out, oc, tr, dets, counts)
+        if seg:  # the predicted masks (one sync for the counts), re-ordered like the boxes (U/trackers/track.py:83-84)
+            lazy.mask_src = (self._masks(s, det, cnt.tolist(), args, [(h, w)] * b), idx[0])
         t2 = time.perf_counter()
         speed = {"preprocess": (t1 - t0) * 1e3 / b, "inference": (t2 - t1) * 1e3 / b, "postprocess": 0.0}
-        lazy = LazyTracks(ts, out, oc, tr, dets, counts)
         hwc = _LazyHWC(im, scale)
         names = self.model.names
         return [Results(lambda i=i: hwc[i], path=f"image{i}.jpg", names=names, speed=speed, orig_shape=(h, w),
-                        boxes=lambda i=i: lazy[i]) for i in range(b)]
+                        boxes=lambda i=i: lazy[i], masks=(lambda i=i: lazy.masks(i)) if seg else None)
+                for i in range(b)]
 
     def _track_frames(self, frames, args, dev, topt, paths=None):
         from .preprocess import letterbox_batch, scale_boxes
@@ -658,19 +710,24 @@ class Model:
         ts = self._tracker_state(dev, cfg, args["max_det"], track_rows, b, persist, max_tracks)
         s = self.session(b, h, w, **kw)
         t1 = time.perf_counter()
-        _, (det, cnt) = self._launch(s, (b, h, w), kw, lambda s, _: s(im))
+        s, (det, cnt) = self._launch(s, (b, h, w), kw, lambda s, _: s(im))
         # scale_boxes to each frame's own coordinates (rows past the count scale to garbage nobody reads), then the
         # same kernel over them with the frame's shape as the clip extent
         dets, counts = det.clone(), cnt.clone()
         shapes = [tuple(f.shape[:2]) for f in frames]
         for i, shp in enumerate(shapes):
             scale_boxes((h, w), dets[i], shp)
-        out, oc, tr = ts.update(dets, counts, shapes, reset_each=not persist)
+        seg = self.model.segment
+        out, oc, tr, *idx = ts.update(dets, counts, shapes, reset_each=not persist, want_idx=seg)
         lazy = LazyTracks(ts, out, oc, tr, dets, counts)
+        if seg:  # the predicted masks (one sync for the counts), re-ordered like the boxes (U/trackers/track.py:83-84)
+            ch = counts.tolist()
+            lazy.mask_src = (self._masks(s, det, ch, args, shapes, [dets[i, : ch[i]] for i in range(b)]), idx[0])
         t2 = time.perf_counter()
         speed = {"preprocess": (t1 - t0) * 1e3 / b, "inference": (t2 - t1) * 1e3 / b, "postprocess": 0.0}
         return [Results(f, path=paths[i] if paths else f"image{i}.jpg", names=self.model.names, speed=speed,
-                        boxes=lambda i=i: lazy[i]) for i, f in enumerate(frames)]
+                        boxes=lambda i=i: lazy[i], masks=(lambda i=i: lazy.masks(i)) if seg else None)
+                for i, f in enumerate(frames)]
 
     def val(self, data=None, *, coco_eval=False, loss=False, **kwargs):
         """Detection mAP (U/engine/model.py:609-643): ``data`` = a data YAML, a dataset folder, an image folder /
@@ -700,8 +757,25 @@ class Model:
             from ..nn.tasks import check_e2e_loss
 
             check_e2e_loss(self.model)  # an end2end model's criterion is E2EDetectLoss: before any device work
+        if self.model.segment:
+            _warn_seg_val()
         self.validator = DetectionValidator(self, args)  # kept: its per-image stats (tp, conf, pred_cls, target_cls)
         return self.validator(data)
+
+
+_SEG_VAL_WARNED = False
+
+
+def _warn_seg_val():
+    """val() on a segmentation model: the box report, as for Detect; the mask metrics (SegmentationValidator,
+    SegmentMetrics) are not computed.  Said once."""
+    global _SEG_VAL_WARNED
+    if not _SEG_VAL_WARNED:
+        import warnings
+
+        warnings.warn("val() on a segmentation model reports the box metrics only: mask metrics (mask mAP) are not "
+                      "computed", stacklevel=3)
+        _SEG_VAL_WARNED = True
 
 
 class YOLO(Model):

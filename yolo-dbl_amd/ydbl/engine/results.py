@@ -1,4 +1,4 @@
-"""Results / Boxes containers: the `boxes` subset of U/engine/results.py:187-1110.
+"""Results / Boxes / Masks containers: the `boxes` and `masks` subset of U/engine/results.py:187-1202.
 
 ``Boxes.data`` is ``[n, 6] = x1, y1, x2, y2, conf, cls`` exactly as the
 reference builds it in DetectionPredictor.postprocess
@@ -118,12 +118,63 @@ class Boxes:
         return x
 
 
-class Results:
-    """U/engine/results.py:187- (detection subset: boxes, names, orig_shape, speed)."""
+_NO_POLYGONS = ("mask polygons need cv2's contour tracing (findContours), which is not available here; "
+                "Masks.data holds the binary masks")
 
-    def __init__(self, orig_img, path, names, boxes=None, speed=None, orig_shape=None):
-        """orig_img / boxes may also be zero-argument callables producing them (predict() hands over per-image views
-        of its batch buffers that way: built on first access, not for every image of every batch)."""
+
+class Masks:
+    """U/engine/results.py:1113-1202 — the instance masks of one image: ``data`` [k, H, W], 0 / 1 in fp32 (the
+    reference's) or uint8 (predict(mask_dtype=torch.uint8)), one plane per box, in box order.  ``xy`` / ``xyn`` (the
+    polygon forms) raise NotImplementedError: they need cv2's contour tracing."""
+
+    def __init__(self, masks, orig_shape):
+        if masks.ndim == 2:
+            masks = masks[None, :]
+        self.data = masks
+        self.orig_shape = tuple(orig_shape)
+
+    def _new(self, data):
+        return Masks(data, self.orig_shape)
+
+    def cpu(self):
+        return self._new(self.data.cpu()) if isinstance(self.data, torch.Tensor) else self
+
+    def numpy(self):
+        return self._new(self.data.cpu().numpy() if isinstance(self.data, torch.Tensor) else self.data)
+
+    def cuda(self):
+        return self._new(torch.as_tensor(self.data).cuda())
+
+    def to(self, *args, **kwargs):
+        return self._new(torch.as_tensor(self.data).to(*args, **kwargs))
+
+    def __len__(self):
+        return len(self.data)
+
+    def __getitem__(self, idx):
+        return self._new(self.data[idx])
+
+    @property
+    def shape(self):
+        return self.data.shape
+
+    @property
+    def xy(self):
+        raise NotImplementedError(_NO_POLYGONS)
+
+    @property
+    def xyn(self):
+        raise NotImplementedError(_NO_POLYGONS)
+
+
+class Results:
+    """U/engine/results.py:187- (boxes, masks, names, orig_shape, speed)."""
+
+    def __init__(self, orig_img, path, names, boxes=None, speed=None, orig_shape=None, masks=None):
+        """orig_img / boxes / masks may also be zero-argument callables producing them (predict() hands over per-image
+        views of its batch buffers that way: built on first access, not for every image of every batch).  masks: a
+        [k, H, W] tensor, or None -- as for an image without detections (U/models/yolo/segment/predict.py:86-87)."""
+        self._masks_src, self._masks = masks, None
         self._orig_img = orig_img
         if orig_shape is None and orig_img is not None:
             orig_shape = (orig_img() if callable(orig_img) else orig_img).shape[:2]
@@ -154,6 +205,17 @@ class Results:
     def boxes(self, v):
         self._boxes, self._boxes_src = v, None
 
+    @property
+    def masks(self):
+        if self._masks is None and self._masks_src is not None:
+            src = self._masks_src() if callable(self._masks_src) else self._masks_src
+            self._masks, self._masks_src = (Masks(src, self.orig_shape) if src is not None else None), None
+        return self._masks
+
+    @masks.setter
+    def masks(self, v):
+        self._masks, self._masks_src = v, None
+
     def __len__(self):
         return 0 if self.boxes is None else len(self.boxes)
 
@@ -164,15 +226,19 @@ class Results:
         r = self.new()
         if self.boxes is not None:
             r.boxes = getattr(self.boxes, fn)(*args, **kwargs)
+        if self.masks is not None:
+            r.masks = getattr(self.masks, fn)(*args, **kwargs)
         return r
 
     def new(self):
         return Results(self._orig_img, self.path, self.names, None, self.speed, orig_shape=self.orig_shape)
 
-    def update(self, boxes=None):
-        """U/engine/results.py:308-334 (boxes): clip to the original image and replace."""
+    def update(self, boxes=None, masks=None):
+        """U/engine/results.py:308-334: boxes clipped to the original image and replaced; masks replaced."""
         if boxes is not None:
             self.boxes = Boxes(_clip_boxes(boxes, self.orig_shape), self.orig_shape)
+        if masks is not None:
+            self.masks = Masks(masks, self.orig_shape)
 
     def cpu(self):
         return self._apply("cpu")
@@ -189,6 +255,8 @@ class Results:
     def save_txt(self, txt_file, save_conf=False):
         """U/engine/results.py:665-718 (detection): 'cls xc yc w h [conf]' normalized, appended."""
         texts = []
+        if self.masks is not None:  # the reference writes the mask's polygon in place of the box (:702-705)
+            raise NotImplementedError("save_txt of a result with masks: " + _NO_POLYGONS)
         if self.boxes is not None and len(self.boxes):
             b = self.boxes.cpu() if isinstance(self.boxes.data, torch.Tensor) else self.boxes
             xywhn = torch.as_tensor(b.xywhn)
@@ -215,9 +283,13 @@ class Results:
     def to_json(self, normalize=False, decimals=5):
         return json.dumps(self.summary(normalize=normalize, decimals=decimals), indent=2)
 
-    def plot(self, conf=True, line_width=None, labels=True, boxes=True, img=None):
-        """Annotated copy of the original image (HWC uint8 BGR ndarray, like the reference's plot())."""
+    def plot(self, conf=True, line_width=None, labels=True, boxes=True, img=None, masks=True):
+        """Annotated copy of the original image (HWC uint8 BGR ndarray, like the reference's plot()).  Mask drawing is
+        not implemented: a result with masks raises NotImplementedError unless masks=False (boxes only)."""
         from PIL import Image, ImageDraw
+
+        if masks and self.masks is not None:
+            raise NotImplementedError("plot() does not draw masks; plot(masks=False) draws the boxes alone")
 
         im = self.orig_img if img is None else img
         if isinstance(im, torch.Tensor):  # CHW/HWC float 0..1 tensor source -> HWC uint8 BGR
@@ -256,6 +328,8 @@ class Results:
 
     def summary(self, normalize=False, decimals=5):
         out = []
+        if self.masks is not None:  # the reference adds a "segments" column of polygon points (:805-812)
+            raise NotImplementedError("summary of a result with masks: " + _NO_POLYGONS)
         if self.boxes is None:
             return out
         h, w = self.orig_shape

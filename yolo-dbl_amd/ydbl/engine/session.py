@@ -116,6 +116,34 @@ class _EagerSlot:
         self.s._set_slot(0)
 
 
+def is_segment(model) -> bool:
+    """The model's head is a Segment (U/nn/modules/head.py:224-271): its sessions also produce masks."""
+    from ..nn.modules import Segment
+
+    return isinstance(model.model[-1], Segment)
+
+
+def check_segment(model, fp8=False, loss=None, gather_rows=None):
+    """A segmentation model's scope guards, on the host before any device work: no fp8 (no calibration record covers
+    Proto and the coefficient branch), no loss (the criterion is v8SegmentationLoss, U/utils/loss.py) and no
+    batch-sharded predictor (its record rows carry boxes only)."""
+    if not is_segment(model):
+        return
+    if fp8:
+        raise NotImplementedError("fp8=True on a segmentation model: no calibration record exists for Proto and the "
+                                  "mask-coefficient branch")
+    if loss is not None and loss is not False:
+        raise NotImplementedError("the loss of a segmentation model is v8SegmentationLoss, which is not implemented")
+    if gather_rows is not None:
+        raise NotImplementedError("segmentation models are not implemented for the batch-sharded predictor "
+                                  "(gather_rows): its record rows carry boxes only")
+
+
+def _f32(v: float) -> float:
+    """v rounded to fp32, as torch does when it multiplies a Python float into an fp32 tensor."""
+    return torch.tensor(v, dtype=torch.float32).item()
+
+
 def _det_count(batch: int, max_det: int, dev):
     """det [B, max_det, 6] fp32 and count [B] int32 as views of ONE zeroed buffer (flat), so a caller keeping a batch's
     outputs past the next launch copies them in one go (predict())."""
@@ -240,6 +268,7 @@ class DetectSession(BatchSession):
             from ..nn.tasks import check_e2e_loss
 
             check_e2e_loss(model)
+        check_segment(model, opt.fp8, opt.loss, gather_rows)  # a Segment head: no fp8, loss or record rows
         if opt.fp8:
             for name in ("C2PSA", "SPPF"):
                 if any(type(m).__name__ == name for m in model.modules()):
@@ -302,6 +331,7 @@ class DetectSession(BatchSession):
         self.conf, self.iou, self.max_det = float(opt.conf), float(opt.iou), int(opt.max_det)
         self.nc = model.model[-1].nc
         self.det = self.count = self.pred = None
+        self.segment = is_segment(model)  # a Segment head: the NMS also writes keep_idx, masks() reads plan.seg
 
     def _alloc_outputs(self, A: int):
         self.det, self.count, self.out_flat = _det_count(self.batch, self.max_det, self.device)
@@ -381,6 +411,10 @@ class DetectSession(BatchSession):
         self.classes_t = torch.tensor(list(classes), dtype=torch.int32, device=dev) if classes is not None else None
         self._nms_ws = torch.zeros(int(_lib.lib.ydbl_nms_workspace(batch, cap, self.opt.max_nms)), dtype=torch.uint8,
                                    device=dev)
+        self.keep_idx = None
+        if self.segment:  # per kept row the candidate's index: finds its mask coefficients (ydbl_nms_desc.out_idx)
+            self.keep_idx = torch.full((batch, self.max_det), -1, dtype=torch.int32, device=dev)
+            plan.buffers.append(self.keep_idx)
         plan.buffers += [self.cand_box, self.cand_score, self.cand_cls, self.cand_idx, self._cand_count, self.det,
                          self.count, self._nms_ws]
 
@@ -406,7 +440,8 @@ class DetectSession(BatchSession):
                      self.cand_idx.data_ptr(), self._cand_count.data_ptr(), self.batch, self.cap, self.iou, self.max_det,
                      int(opt.max_nms), int(bool(opt.agnostic)), float(opt.max_wh), float(w) if opt.clip else 0.0,
                      float(h) if opt.clip else 0.0, self.det.data_ptr(), self.count.data_ptr(), self._nms_ws.data_ptr(),
-                     self.det.stride(0), self.count.stride(0), int(self.conf >= PER_IMAGE_NMS_CONF))
+                     self.det.stride(0), self.count.stride(0), int(self.conf >= PER_IMAGE_NMS_CONF),
+                     self.keep_idx.data_ptr() if self.keep_idx is not None else None)
         plan.launch("ydbl_nms", nd, what="NMS", keep=[nd])
 
     def _emit_loss(self, plan: Plan, cm, dd: DecodeDesc, cfg: dict):
@@ -506,6 +541,80 @@ class DetectSession(BatchSession):
         plan.steps = steps
         return True
 
+    # ------------------------------------------------------------------ instance masks (a Segment head)
+    def seg_outputs(self):
+        """(mc [B, nm, A], p [B, nm, mh, mw]) of the last launch as fresh tensors of the session's dtype: the
+        reference's Segment.forward outputs (U/nn/modules/head.py:259-271)."""
+        from ..nn.modules import seg_coefficients
+
+        if not self.segment:
+            raise RuntimeError("seg_outputs(): the model's head is not a Segment")
+        segs = [p.compiled.plan.seg for p in self.parts]
+        return (torch.cat([seg_coefficients(mcs) for _, mcs in segs]),
+                torch.cat([proto.nchw().contiguous() for proto, _ in segs]))
+
+    def _mask_views(self, part, i=None):
+        """The proto and coefficient views of one sub-batch plan (whole, or image i of it alone) as _lib.View."""
+        proto, mcs = part.compiled.plan.seg
+        if i is None:
+            return proto.struct(), [v.struct() for v in mcs]
+
+        def one(v):
+            st = v.struct()
+            st.ptr += i * v.h * v.w * v.cs * v.base.element_size()
+            st.n = 1
+            return st
+
+        return one(proto), [one(v) for v in mcs]
+
+    def masks(self, counts, dtype=torch.float32):
+        """process_mask(upsample=True) of the last launch's detections (U/models/yolo/segment/predict.py:56-57): one
+        ydbl_process_mask launch per sub-batch plan on the current stream, reading the plan's proto and coefficient
+        buffers and the session's det / count / keep_idx in place -- call it before the session is launched again.
+        counts: the host copy of self.count.  -> (masks [sum(counts), h, w] 0 / 1 in `dtype`, offsets [B + 1])."""
+        from ..utils.ops import launch_process_mask
+
+        if not self.segment or not self.opt.nms:
+            raise RuntimeError("masks(): needs a Segment head and a session with nms=True")
+        offs = [0]
+        for c in counts:
+            offs.append(offs[-1] + int(c))
+        out = torch.empty((offs[-1], self.h, self.w), dtype=dtype, device=self.device)
+        if offs[-1] == 0:
+            return out, offs
+        row = torch.tensor(offs[:-1], dtype=torch.int64).to(self.device, non_blocking=True)
+        for part, (a, b) in zip(self.parts, self.bounds):
+            slots = max(counts[a:b])
+            if slots == 0:
+                continue
+            pv, mcv = self._mask_views(part)
+            launch_process_mask(pv, self.det[a:b], self.count[a:b], row[a:b], out, (self.h, self.w),
+                                window=(0, 0, pv.h, pv.w), sx=_f32(pv.w / self.w), sy=_f32(pv.h / self.h),
+                                crop_after=False, max_det=self.max_det, det_stride=self.det.stride(0),
+                                keep_idx=part.keep_idx, mc=mcv, nc=self.nc if part.multi_label else 0, slots=slots)
+        return out, offs
+
+    def masks_native(self, i, boxes, shape, dtype=torch.float32):
+        """process_mask_native of image i of the last launch (retina_masks, predict.py:53-55): boxes [k, >= 4] fp32 on
+        the device, already scaled to `shape` = the original image's (h, w), row j the session's j-th kept detection
+        of the image.  One launch on the current stream -> masks [k, shape[0], shape[1]] 0 / 1 in `dtype`."""
+        from ..utils.ops import launch_process_mask, mask_window
+
+        if not self.segment or not self.opt.nms:
+            raise RuntimeError("masks_native(): needs a Segment head and a session with nms=True")
+        k = boxes.shape[0]
+        out = torch.empty((k, int(shape[0]), int(shape[1])), dtype=dtype, device=self.device)
+        if k == 0:
+            return out
+        part, a = next((p, a) for p, (a, b) in zip(self.parts, self.bounds) if a <= i < b)
+        pv, mcv = self._mask_views(part, i - a)
+        boxes = boxes.contiguous()
+        zero = torch.zeros(1, dtype=torch.int64, device=self.device)
+        launch_process_mask(pv, boxes, self.count[i:i + 1], zero, out, shape, window=mask_window(pv.h, pv.w, shape),
+                            sx=1.0, sy=1.0, crop_after=True, max_det=self.max_det, det_row=boxes.shape[1],
+                            keep_idx=part.keep_idx[i - a], mc=mcv, nc=self.nc if part.multi_label else 0, slots=k)
+        return out
+
     @property
     def cand_count(self):
         """Candidates per image of the last launch (a split session's: its sub-batches' counters, concatenated)."""
@@ -516,6 +625,8 @@ class DetectSession(BatchSession):
         """launch_bound() takes x: a contiguous fp32 tensor of the session's shape on its device, every sub-batch 16-byte
         aligned (the stem kernels' vector loads)."""
         if self.records is not None:  # gather_rows: the NMS writes record rows (out_stride = record width), not slots
+            return False
+        if self.segment:  # the masks are assembled from the session's own det / count / keep_idx after the replay
             return False
         if (not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.device != self.det.device
                 or not x.is_contiguous() or tuple(x.shape) != (self.batch, 3, self.h, self.w)

@@ -129,16 +129,18 @@ class TrackerState:
                                              device=self.device)
         return t
 
-    def update(self, det: torch.Tensor, count: torch.Tensor, shapes, reset_each: bool):
+    def update(self, det: torch.Tensor, count: torch.Tensor, shapes, reset_each: bool, want_idx: bool = False):
         """Enqueue one ydbl_bytetrack_update on the current stream over det [n, max_det, 6] / count [n] (any row
         strides: a session's buffers are read in place).  shapes: each image's (h, w).  -> out [n, max_det, 7],
-        out_count [n], tracked [n] (device tensors; nothing is synchronised)."""
+        out_count [n], tracked [n] (device tensors; nothing is synchronised); want_idx: also out_idx [n, max_det]
+        int32, each track row's detection index (-1 past the count)."""
         n = det.shape[0]
         assert det.shape[1] == self.max_det and det.dtype == torch.float32 and count.dtype == torch.int32
         assert det.stride(2) == 1 and det.stride(1) == 6
         out = torch.empty((n, self.max_det, 7), dtype=torch.float32, device=self.device)
         oc = torch.empty(2 * n, dtype=torch.int32, device=self.device)
         hw = self.hw_tensor(shapes)
+        idx = torch.empty((n, self.max_det), dtype=torch.int32, device=self.device) if want_idx else None
         cfg = self.cfg
         d = self._lib.TrackDesc(
             det=det.data_ptr(), det_count=count.data_ptr(), n=n, max_det=self.max_det, det_stride=det.stride(0),
@@ -147,11 +149,11 @@ class TrackerState:
             match_thresh=cfg["match_thresh"], fuse_score=int(cfg["fuse_score"]), track_buffer=cfg["track_buffer"],
             max_time_lost=max_time_lost(cfg), max_tracks=self.max_tracks, trackers=self.trackers,
             reset_each=int(bool(reset_each)), out=out.data_ptr(), out_count=oc.data_ptr(),
-            tracked=oc.data_ptr() + 4 * n, out_idx=None, state=self.buf.data_ptr(),
+            tracked=oc.data_ptr() + 4 * n, out_idx=idx.data_ptr() if want_idx else None, state=self.buf.data_ptr(),
             state_bytes=self.buf.numel())
         stream = torch.cuda.current_stream(self.device).cuda_stream
         self._lib.check(self._lib.lib.ydbl_bytetrack_update(C.byref(d), stream), "ydbl_bytetrack_update")
-        return out, oc[:n], oc[n:]
+        return (out, oc[:n], oc[n:], idx) if want_idx else (out, oc[:n], oc[n:])
 
     def check_overflow(self, total: int):
         """Raise when the overflow counter moved since it was last looked at (a track could not be started)."""
@@ -184,3 +186,15 @@ class LazyTracks:
     def __getitem__(self, i):
         oc, tr, cnt = self._sync()
         return self.out[i, : oc[i]] if tr[i] else self.dets[i, : cnt[i]]
+
+    mask_src = None  # a segmentation model's track(): (i -> the image's predicted masks or None, out_idx)
+
+    def masks(self, i):
+        """Image i's masks in the order of its boxes: the predicted masks picked by the track rows' detection indices
+        when the image got tracks (results[i][idx], U/trackers/track.py:83-84), else as predicted; None without one."""
+        oc, tr, _ = self._sync()
+        fn, idx = self.mask_src
+        m = fn(i)
+        if m is None or not tr[i]:
+            return m
+        return m[idx[i, : oc[i]].long()]

@@ -1699,6 +1699,84 @@ class E2ETail:
         plan.launch("ydbl_detect_topk", self.td, what="TopK", keep=[self.td])
 
 
+def emit_deconv2x2(plan: Plan, m: nn.ConvTranspose2d, x: TV, out: TV | None = None, act=_lib.ACT_NONE) -> TV:
+    """nn.ConvTranspose2d(c, c, 2, 2, 0) as one ydbl_deconv2x2_nhwc launch; the weight is packed here from torch's
+    [cin][cout][2][2] into [2*dy+dx][cout][cin] in the plan dtype (include/ydbl.h)."""
+    if (m.kernel_size != (2, 2) or m.stride != (2, 2) or m.padding != (0, 0) or m.output_padding != (0, 0)
+            or m.dilation != (1, 1) or m.groups != 1):
+        raise NotImplementedError("ConvTranspose2d: only kernel 2, stride 2, pad 0, groups 1 has a HIP kernel")
+    if m.in_channels != x.c or m.in_channels % 32 or m.out_channels % 32:
+        raise NotImplementedError(f"ConvTranspose2d({m.in_channels}, {m.out_channels}) on {x.c} channels: cin and cout "
+                                  "must be multiples of 32")
+    y = out if out is not None else plan.alloc(x.n, 2 * x.h, 2 * x.w, m.out_channels)
+    wd = plan.const(m.weight.detach().float().cpu().permute(2, 3, 1, 0).contiguous().to(plan.dtype))
+    bd = plan.const(m.bias.detach().float().cpu()) if m.bias is not None else None
+    d = _lib.DeconvDesc(x.struct(), y.struct(), wd.data_ptr(), bd.data_ptr() if bd is not None else None, act)
+    plan.launch("ydbl_deconv2x2_nhwc", d, what="deconv2x2", keep=[wd, bd, d])
+    return y
+
+
+class Proto(PlanModule):
+    """U/nn/modules/block.py:87-104 — Conv3x3 -> ConvTranspose2d(c_, c_, 2, 2) -> Conv3x3 -> Conv1x1: the mask
+    prototypes at twice the P3 resolution."""
+
+    def __init__(self, c1, c_=256, c2=32):
+        super().__init__()
+        self.cv1 = Conv(c1, c_, k=3)
+        self.upsample = nn.ConvTranspose2d(c_, c_, 2, 2, 0, bias=True)
+        self.cv2 = Conv(c_, c_, k=3)
+        self.cv3 = Conv(c_, c2)
+
+    def emit(self, plan, x, out=None):
+        t = self.cv1.emit(plan, x)
+        t = emit_deconv2x2(plan, self.upsample, t)
+        t = self.cv2.emit(plan, t)
+        return self.cv3.emit(plan, t, out)
+
+
+class Segment(Detect):
+    """U/nn/modules/head.py:224-271 — Detect plus the mask branch: Proto on the P3 map and, per level, cv4 = Conv3x3 ->
+    Conv3x3 -> Conv2d 1x1 giving nm mask coefficients per anchor.  The coefficients go into a buffer of their own per
+    level ([B, h, w, nm]), so the level buffers [B, h, w, 64 + nc] the decode and the candidate paths read keep
+    their layout.  emit() returns the Detect levels and leaves ``plan.seg = (proto view, [coefficient views])``."""
+
+    def __init__(self, nc: int = 80, nm: int = 32, npr: int = 256, ch: tuple = (), legacy: bool | None = None):
+        super().__init__(nc, ch, legacy)
+        self.nm = nm
+        self.npr = npr
+        self.proto = Proto(ch[0], self.npr, self.nm)
+        c4 = max(ch[0] // 4, self.nm)
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, self.nm, 1)) for x in ch)
+
+    def emit(self, plan, xs, out=None):
+        levels = self._emit_branches(plan, xs, self.cv2, self.cv3)
+        proto = self.proto.emit(plan, xs[0])
+        mcs = []
+        for i, x in enumerate(xs):
+            t = emit_conv3x3_pair(plan, self.cv4[i][0], self.cv4[i][1], x)
+            mcs.append(emit_conv2d(plan, self.cv4[i][2], t, plan.alloc(x.n, x.h, x.w, self.nm), what="Segment.mc"))
+        plan.seg = (proto, mcs)
+        return levels
+
+    def _forward_plan(self, plan, xs):
+        """forward(x) in inference mode (head.py:259-271 with export False): (cat([y, mc], 1) [B, 4+nc+nm, A],
+        (feats, mc [B, nm, A], p [B, nm, mh, mw])) as fresh tensors of the plan's dtype."""
+        det = super()._forward_plan(plan, xs)
+        proto, mcs = plan.seg
+
+        def finish():
+            y, feats = det()
+            mc = seg_coefficients(mcs)
+            return torch.cat([y, mc], 1), (feats, mc, proto.nchw().contiguous())
+
+        return finish
+
+
+def seg_coefficients(mcs) -> torch.Tensor:
+    """The per-level coefficient views [B, h, w, nm] as the reference's mc [B, nm, A] (head.py:264), a fresh tensor."""
+    return torch.cat([v.torch().reshape(v.n, v.h * v.w, v.c) for v in mcs], 1).permute(0, 2, 1).contiguous()
+
+
 def emit_module(m: nn.Module, plan: Plan, x, out=None):
     """Emit any parsed layer: built-in modules (HIP launches), nn.Sequential repeats, and registered plugin
     classes that only have a torch forward (emit_torch)."""

@@ -38,13 +38,14 @@ REGISTRY: dict[str, type] = {
     for c in (M.Conv, M.DWConv, M.DSConv, M.GhostConv, M.Concat, M.Bottleneck, M.C2f, M.C3, M.C3Ghost,
               M.GhostBottleneck, M.DSBottleneck, M.DSC3k, M.DSC3k2, M.HyperACE, M.DownsampleConv,
               M.FullPAD_Tunnel, M.DySample, M.LSKblock, M.Detect, M.AAttn, M.ABlock, M.A2C2f, M.SPPF, M.C3k, M.C3k2,
-              M.Attention, M.PSABlock, M.C2PSA, M.PSA, M.SCDown, M.RepVGGDW, M.CIB, M.C2fCIB, M.v10Detect)
+              M.Attention, M.PSABlock, M.C2PSA, M.PSA, M.SCDown, M.RepVGGDW, M.CIB, M.C2fCIB, M.v10Detect, M.Proto,
+              M.Segment)
 }
 REGISTRY["nn.Upsample"] = M.Upsample  # the one torch.nn layer name the v13 YAMLs use (U/nn/tasks.py:972-973)
 _C1C2 = {"Conv", "DWConv", "GhostConv", "Bottleneck", "GhostBottleneck", "C2f", "C3", "C3Ghost", "DSC3k2", "DSConv",
          "DSBottleneck", "A2C2f", "SPPF", "C3k2", "C2PSA", "PSA", "SCDown", "C2fCIB"}
 _REPEAT_ARG = {"C2f", "C3", "C3Ghost", "DSC3k2", "A2C2f", "C3k2", "C2PSA", "C2fCIB"}
-_DETECT = {"Detect", "v10Detect"}  # U/nn/tasks.py:1107
+_DETECT = {"Detect", "v10Detect", "Segment"}  # U/nn/tasks.py:1107-1112
 _C1_ONLY = {"DySample", "LSKblock"}
 
 
@@ -172,6 +173,8 @@ def parse_model(d: dict, ch: int = 3, verbose: bool = False):
             c2 = sum(ch[x] for x in f)
         elif name in _DETECT:
             args.append([ch[x] for x in f])
+            if name == "Segment":  # U/nn/tasks.py:1109-1110: the proto width scales like a channel count
+                args[2] = make_divisible(min(args[2], max_channels) * width, 8)
         elif name == "HyperACE":
             legacy = False
             c1 = ch[f[1]]
@@ -194,7 +197,7 @@ def parse_model(d: dict, ch: int = 3, verbose: bool = False):
             args = [c1, *args[1:]]
         else:
             c2 = ch[f]
-        if name == "Detect":
+        if name in ("Detect", "Segment"):
             m.legacy = legacy  # class attribute, as the reference sets it (U/nn/tasks.py:1111-1112)
             m_ = m(*args)
             m_.legacy = legacy  # and on the instance: a yolov8 (legacy) and a yolo11 model may live in one process
@@ -228,6 +231,7 @@ class DetectionModel(nn.Module):
         self.inplace = self.yaml.get("inplace", True)
         m = self.model[-1]
         self.end2end = bool(getattr(m, "end2end", False))  # U/nn/tasks.py:331
+        self.segment = isinstance(m, M.Segment)  # SegmentationModel (U/nn/tasks.py:439-452): the same forward
         # Stride probe by shape propagation at 256x256 (the reference runs a train-mode forward on
         # zeros, U/nn/tasks.py:337-350; only its output shapes are used for the strides).
         s = 256
@@ -290,11 +294,17 @@ class DetectionModel(nn.Module):
             if augment:
                 warn_e2e_augment()
             return self._run(x, e2e=True)[1]
+        if self.segment and augment:  # _predict_augment (U/nn/tasks.py:361-366): any class but DetectionModel
+            warn_no_augment()
+            augment = False
         s, _ = self._run(x, augment=augment)
         y = s.pred.to(x.dtype, copy=True)
         if augment:
             return y, None
         feats = [f.contiguous() for f in s.feats()]
+        if self.segment:  # Segment.forward (U/nn/modules/head.py:259-271): (cat([y, mc], 1), (feats, mc, p))
+            mc, p = s.seg_outputs()
+            return torch.cat([y, mc], 1), (feats, mc, p)
         return y, feats
 
     MAX_LABELS = 300  # per image: the capacity of the in-graph loss's label buffer (loss(batch) with preds=None)
@@ -545,9 +555,26 @@ def warn_e2e_augment():
         _E2E_AUGMENT_WARNED = True
 
 
+def warn_no_augment():
+    """_predict_augment on a model that is not a plain DetectionModel (U/nn/tasks.py:361-366; a segmentation model):
+    a warning, once, and the plain pass."""
+    global _SEG_AUGMENT_WARNED
+    if not _SEG_AUGMENT_WARNED:
+        import warnings
+
+        warnings.warn("Model does not support 'augment=True', reverting to single-scale prediction.", stacklevel=3)
+        _SEG_AUGMENT_WARNED = True
+
+
+_SEG_AUGMENT_WARNED = False
+
+
 def check_e2e_loss(model):
     """The criterion of an end2end model is E2EDetectLoss (U/utils/loss.py:728-743), the dual-assignment loss over
-    both branch sets: not implemented.  Raised on the host, before any device work."""
+    both branch sets: not implemented.  Nor is a segmentation model's (v8SegmentationLoss).  Raised on the host, before
+    any device work."""
+    if getattr(model, "segment", False):
+        raise NotImplementedError("the loss of a segmentation model is v8SegmentationLoss, which is not implemented")
     if getattr(model, "end2end", False):
         raise NotImplementedError("the loss of an end2end (YOLOv10) model is E2EDetectLoss (one2many + one2one "
                                   "assignment), which is not implemented")

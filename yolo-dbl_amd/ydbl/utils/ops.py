@@ -113,3 +113,114 @@ def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=Non
     _lib.check(_lib.lib.ydbl_nms(nd, stream), "ydbl_nms")
     counts = cnt.tolist()
     return [out[i, : counts[i]] for i in range(bs)]
+
+
+# ----------------------------------------------------------------------------- instance masks (U/utils/ops.py:644-737)
+MASK_MAX_DET = 4096  # ydbl_process_mask: detection slots per image and launch
+
+
+def mask_dtype_code(dtype) -> int:
+    """ydbl_mask_desc.out_dtype of a torch dtype: float32 (the reference's masks) or uint8."""
+    if dtype in (None, torch.float32):
+        return _lib.MASK_F32
+    if dtype == torch.uint8:
+        return _lib.MASK_U8
+    raise ValueError(f"mask_dtype {dtype}: torch.float32 or torch.uint8 expected")
+
+
+def mask_window(mh: int, mw: int, shape, padding: bool = True) -> tuple:
+    """scale_masks' crop of an (mh, mw) grid for a target `shape` (U/utils/ops.py:726-734): (top, left, bottom,
+    right), the letterbox padding on the proto grid cut away.  Python float arithmetic, as the reference's."""
+    gain = min(mh / shape[0], mw / shape[1])
+    pad = [mw - shape[1] * gain, mh - shape[0] * gain]
+    if padding:
+        pad[0] /= 2
+        pad[1] /= 2
+    top, left = (int(pad[1]), int(pad[0])) if padding else (0, 0)
+    bottom, right = int(mh - pad[1]), int(mw - pad[0])
+    return top, left, bottom, right
+
+
+def launch_process_mask(proto, det, count, row_offset, out, out_hw, *, window, sx, sy, crop_after, max_det,
+                        det_stride=0, det_row=0, coef=None, keep_idx=None, mc=(), nc=0, slots=0, stream=None):
+    """One ydbl_process_mask launch (include/ydbl.h).  proto: a _lib.View [n, mh, mw, nm]; det / count / row_offset /
+    out / coef / keep_idx: device tensors or raw pointers; mc: the level Views when keep_idx names the anchors."""
+    ptr = lambda t: t.data_ptr() if isinstance(t, torch.Tensor) else t  # noqa: E731
+    d = _lib.MaskDesc()
+    d.proto = proto
+    for i, v in enumerate(mc):
+        d.mc[i] = v
+    d.nl, d.nc, d.keep_idx = len(mc), int(nc), ptr(keep_idx)
+    d.det, d.det_stride, d.det_row, d.max_det = ptr(det), int(det_stride), int(det_row), int(max_det)
+    d.count, d.coef, d.row_offset, d.out = ptr(count), ptr(coef), ptr(row_offset), ptr(out)
+    d.out_h, d.out_w = int(out_hw[0]), int(out_hw[1])
+    d.out_dtype = mask_dtype_code(out.dtype) if isinstance(out, torch.Tensor) else _lib.MASK_F32
+    d.top, d.left, d.bottom, d.right = (int(v) for v in window)
+    d.sx, d.sy, d.crop_after, d.slots = float(sx), float(sy), int(bool(crop_after)), int(slots)
+    if stream is None:
+        stream = torch.cuda.current_stream(out.device).cuda_stream
+    _lib.check(_lib.lib.ydbl_process_mask(d, stream), "ydbl_process_mask")
+
+
+def _masks_direct(protos, masks_in, bboxes, out_hw, window, sx, sy, crop_after):
+    """process_mask / process_mask_native of one image on the GPU: protos [c, mh, mw], masks_in [n, c], bboxes
+    [n, 4] -> fp32 0 / 1 masks [n, H, W].  More than MASK_MAX_DET rows go in several launches."""
+    if not (isinstance(protos, torch.Tensor) and protos.is_cuda):
+        raise RuntimeError("ydbl mask ops run on the GPU only (protos must be a CUDA tensor)")
+    if protos.dtype not in (torch.float16, torch.float32):
+        raise TypeError(f"protos dtype {protos.dtype}: float32 or float16 expected")
+    c, mh, mw = protos.shape
+    n = masks_in.shape[0]
+    dev = protos.device
+    out = torch.empty((n, int(out_hw[0]), int(out_hw[1])), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    p = protos.permute(1, 2, 0).contiguous()  # NHWC, one image
+    pv = _lib.View(p.data_ptr(), 1, mh, mw, c, c, _lib.dtype_code(p.dtype))
+    coef = masks_in.detach().to(dev, torch.float32).contiguous()
+    box = bboxes.detach().to(dev, torch.float32)[:, :4].contiguous()
+    zero = torch.zeros(1, dtype=torch.int64, device=dev)
+    for a in range(0, n, MASK_MAX_DET):
+        k = min(MASK_MAX_DET, n - a)
+        cnt = torch.full((1,), k, dtype=torch.int32, device=dev)
+        launch_process_mask(pv, box[a:a + k], cnt, zero, out[a:a + k], out_hw, window=window, sx=sx, sy=sy,
+                            crop_after=crop_after, max_det=k, det_row=4, coef=coef[a:a + k])
+    return out
+
+
+def crop_mask(masks, boxes):
+    """U/utils/ops.py:644-658: masks [n, h, w] times the box indicator (r >= x1, r < x2, c >= y1, c < y2 on float
+    indices).  Elementwise torch on the tensors' device; the mask path proper fuses it (ydbl_process_mask)."""
+    _, h, w = masks.shape
+    x1, y1, x2, y2 = torch.chunk(boxes[:, :, None], 4, 1)
+    r = torch.arange(w, device=masks.device, dtype=x1.dtype)[None, None, :]
+    c = torch.arange(h, device=masks.device, dtype=x1.dtype)[None, :, None]
+    return masks * ((r >= x1) * (r < x2) * (c >= y1) * (c < y2))
+
+
+def process_mask(protos, masks_in, bboxes, shape, upsample=False):
+    """U/utils/ops.py:661-693 as one ydbl_process_mask launch: protos [c, mh, mw] (fp16 / fp32, CUDA), masks_in
+    [n, c], bboxes [n, 4] in `shape` = (ih, iw) pixels -> fp32 0 / 1 masks [n, ih, iw] (upsample) or [n, mh, mw]."""
+    c, mh, mw = protos.shape
+    ih, iw = shape
+    sx = torch.tensor(mw / iw, dtype=torch.float32).item()  # the ratio as torch multiplies it into an fp32 tensor
+    sy = torch.tensor(mh / ih, dtype=torch.float32).item()
+    out_hw = (ih, iw) if upsample else (mh, mw)
+    return _masks_direct(protos, masks_in, bboxes, out_hw, (0, 0, mh, mw), sx, sy, False)
+
+
+def process_mask_native(protos, masks_in, bboxes, shape):
+    """U/utils/ops.py:696-713: the proto-grid masks resampled to `shape` through scale_masks' window, cropped to the
+    boxes (in `shape` pixels) afterwards -> fp32 0 / 1 masks [n, shape[0], shape[1]]."""
+    c, mh, mw = protos.shape
+    return _masks_direct(protos, masks_in, bboxes, shape, mask_window(mh, mw, shape), 1.0, 1.0, True)
+
+
+def scale_masks(masks, shape, padding=True):
+    """U/utils/ops.py:716-737: masks [N, C, H, W] cropped to mask_window and resampled bilinearly to `shape`, values
+    kept (no threshold) -- torch's own interpolate on the tensors' device; ydbl_process_mask does the same resampling
+    fused with the coefficient product and the threshold."""
+    mh, mw = masks.shape[2:]
+    top, left, bottom, right = mask_window(mh, mw, shape, padding)
+    masks = masks[..., top:bottom, left:right]
+    return torch.nn.functional.interpolate(masks, shape, mode="bilinear", align_corners=False)
