@@ -69,6 +69,10 @@
  *   ydbl_match_predictions <- DetectionValidator._process_batch models/yolo/detect/val.py:209-227
  *                             (box_iou utils/metrics.py:52-71 + BaseValidator.match_predictions
  *                             engine/validator.py:222-262, non-scipy branch)
+ *   ydbl_gt_mask_bits      <- SegmentationValidator._process_batch(masks=True) models/yolo/segment/val.py:204-212
+ *                             (the index map's indicator, F.interpolate bilinear, > 0.5), as bit planes
+ *   ydbl_mask_iou          <- mask_iou utils/metrics.py:137-153 as segment/val.py:213 calls it, popcount on bit planes
+ *   ydbl_match_iou         <- segment/val.py:217: match_predictions on the mask IoU matrix
  *   ydbl_confusion_matrix  <- ConfusionMatrix.process_batch utils/metrics.py:326-382 and its call sites in
  *                             DetectionValidator.update_metrics models/yolo/detect/val.py:140-159
  *   ydbl_coco_match        <- COCOeval.evaluateImg (the COCO detection protocol's per-image, per-category greedy
@@ -961,6 +965,9 @@ int ydbl_deconv2x2_nhwc(const ydbl_deconv_desc* d, void* stream);
  *     -- process_mask_native with sx = sy = 1 and scale_masks' window.
  * The plane of (b, k) is out + (row_offset[b] + k) * out_h * out_w elements, fp32 0 / 1 (YDBL_MASK_F32, the
  * reference's) or uint8 0 / 1 (YDBL_MASK_U8); slots at or past the count write nothing.
+ * YDBL_MASK_BITS: the same values as bit planes, out_h * ceil(out_w / 64) uint64 words per plane, (b, k) at
+ * out + (row_offset[b] + k) * out_h * ceil(out_w / 64) words; bit j of word q of a row is pixel 64 q + j, bits past
+ * out_w are 0; out 8-byte aligned.  1/32 of the fp32 bytes: what ydbl_mask_iou reads.
  * Coefficients: coef != NULL: fp32 [n][max_det][nm] given directly (mc, keep_idx unused).  Otherwise keep_idx
  * int32 [n][max_det] (ydbl_nms's out_idx) names the anchor -- keep_idx itself when nc == 0, keep_idx / nc for the
  * multi-label index anchor * nc + cls -- and the coefficients are that anchor's nm values of the level maps
@@ -972,7 +979,7 @@ int ydbl_deconv2x2_nhwc(const ydbl_deconv_desc* d, void* stream);
  * the grid, 0 = max_det; a caller that knows max(count) passes it to launch no idle workgroups (slots past it are
  * not written).  No atomics, every element of a live slot written once: bit-identical from run to run.  One launch
  * on `stream`, no allocation, no sync. */
-enum { YDBL_MASK_F32 = 0, YDBL_MASK_U8 = 1 };
+enum { YDBL_MASK_F32 = 0, YDBL_MASK_U8 = 1, YDBL_MASK_BITS = 2 };
 typedef struct {
   ydbl_view proto;
   ydbl_view mc[3];
@@ -992,6 +999,81 @@ typedef struct {
   int32_t slots;
 } ydbl_mask_desc;
 int ydbl_process_mask(const ydbl_mask_desc* d, void* stream);
+
+/* Ground-truth masks of a batch as bit planes in the layout of YDBL_MASK_BITS, and their areas: the first half of
+ * SegmentationValidator._process_batch(masks=True) (models/yolo/segment/val.py:204-212).  Labels are grouped by image
+ * as in ydbl_match_desc (gt_ofs int32 [n+1]); label g = gt_ofs[b] + l is image b's l-th label.
+ *   overlap != 0: src is the index map uint8 [n][gh][gw]; label g's indicator is src[b] == l + 1 (the reference's
+ *     torch.where(gt_masks == index, 1.0, 0.0), val.py:206-209); at most 255 labels of an image can be named;
+ *   overlap == 0: src is uint8 planes [n_gt][gh][gw] in grouped label order, nonzero = set.
+ * (gh, gw) == (out_h, out_w): the indicator is copied.  Otherwise it is resampled bilinearly to (out_h, out_w) and
+ * compared with > 0.5 (val.py:210-212: F.interpolate(mode="bilinear", align_corners=False).gt_(0.5)) by the rule of
+ * ydbl_process_mask: scale = float(in) / out, src = max(scale * (d + 0.5) - 0.5, 0), i0 = int(src),
+ * i1 = min(i0 + 1, in - 1), l1 = src - i0, l0 = 1 - l1, v = h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11),
+ * every operation rounded to fp32 on its own.  At an exact ratio of 4 (mask_ratio, the reference's default) every v
+ * is a dyadic fraction that fp32 holds exactly and none equals 0.5, so the bits are torch's.  At other ratios
+ * torch's own value can differ from this formula in the last bit and exact 0.5 occurs: the result equals torch's
+ * wherever the reference value is not within rounding of 0.5.
+ * bits uint64 [n_gt][out_h][ceil(out_w / 64)] (8-byte aligned; bit j of word q of a row = pixel 64 q + j, bits past
+ * out_w zero), area int32 [n_gt] = the set pixels of each plane.  Each word is one wavefront ballot; no atomics,
+ * every output written once.  One launch on `stream`, no allocation, no sync. */
+typedef struct {
+  const uint8_t* src;
+  int32_t n, gh, gw;
+  int32_t overlap;
+  const int32_t* gt_ofs;
+  int32_t n_gt;
+  int32_t out_h, out_w;
+  uint64_t* bits;
+  int32_t* area;
+} ydbl_gt_bits_desc;
+int ydbl_gt_mask_bits(const ydbl_gt_bits_desc* d, void* stream);
+
+/* Mask IoU of every label against every detection slot of its own image, on bit planes: mask_iou
+ * (utils/metrics.py:137-153) as SegmentationValidator._process_batch calls it (models/yolo/segment/val.py:213).
+ * det_bits: the YDBL_MASK_BITS planes of ydbl_process_mask, (b, k) at (row_offset[b] + k) * out_h * ceil(out_w / 64)
+ * words, k < min(count[b], max_det); gt_bits / area_gt: ydbl_gt_mask_bits' outputs, gt_ofs as there.
+ *   inter(g, k) = popcount(gt[g] & det[b][k]),  area_det(b, k) = popcount(det[b][k]),
+ *   iou = float(inter) / (((float(area_gt) + float(area_det)) - float(inter)) + 1e-7f)      (fp32, no contraction).
+ * out_h * out_w <= 2^24 (else YDBL_EINVAL): the counts are then exact in fp32, so iou is bitwise what the
+ * reference's fp32 matmul / sum / division gives on 0 / 1 masks.
+ * iou fp32 [n_gt][max_det]; inter int32 [n_gt][max_det] and area_det int32 [n][max_det] are optional (NULL skips);
+ * columns / slots at or past the count are written 0.  No atomics, every output element written exactly once:
+ * identical from run to run.  One launch on `stream`, no allocation, no sync. */
+typedef struct {
+  const uint64_t* det_bits;
+  const int64_t* row_offset;
+  const int32_t* count;
+  int32_t n, max_det;
+  const uint64_t* gt_bits;
+  const int32_t* gt_ofs;
+  const int32_t* area_gt;
+  int32_t n_gt;
+  int32_t out_h, out_w;
+  float* iou;
+  int32_t* inter;
+  int32_t* area_det;
+} ydbl_mask_iou_desc;
+int ydbl_mask_iou(const ydbl_mask_iou_desc* d, void* stream);
+
+/* ydbl_match_predictions with the IoU of a pair read from a matrix instead of computed from boxes: the second half of
+ * SegmentationValidator._process_batch(masks=True) (models/yolo/segment/val.py:217, BaseValidator.match_predictions
+ * engine/validator.py:222-262).  iou fp32 [n_gt][max_det] as ydbl_mask_iou writes it (row g: label g against the
+ * slots of its own image); det supplies the class column only.  Everything else -- class mismatch = IoU 0,
+ * single_cls, correct uint8 [n][max_det][n_iou], rows >= det_count zeroed, the workspace of ydbl_match_workspace,
+ * the larger label index on an exact tie -- is ydbl_match_predictions' rule, the same kernel. */
+typedef struct {
+  const float* det; const int32_t* det_count;
+  int32_t n, max_det;
+  const float* iou;
+  const float* gt_cls; const int32_t* gt_ofs;
+  int32_t n_gt;
+  const float* iouv; int32_t n_iou;
+  int32_t single_cls;
+  uint8_t* correct;
+  void* workspace; /* ydbl_match_workspace(n, max_det, n_gt, n_iou) bytes */
+} ydbl_match_iou_desc;
+int ydbl_match_iou(const ydbl_match_iou_desc* d, void* stream);
 
 const char* ydbl_last_error(void);
 const char* ydbl_version(void);

@@ -19,6 +19,10 @@
 // address is aligned and the row holds all four, single stores otherwise.  No atomics, every output element of a live
 // slot written exactly once: bit-identical from run to run.
 //
+// YDBL_MASK_BITS packs the same 0 / 1 values 64 columns to a uint64 word (bit j of word q = column 64 q + j, bits past
+// out_w zero): a tile row is one word.  A thread shifts its four columns' nibble to its place, the 16 lanes of the row
+// OR their words together with four __shfl_xor and the first of them stores; an untouched tile stores zero words.
+//
 // Bilinear follows torch's upsample_bilinear2d: scale = float(in) / out, src = max(scale * (d + 0.5) - 0.5, 0),
 // i0 = int(src), i1 = min(i0 + 1, in - 1), l1 = src - i0, l0 = 1 - l1,
 // v = h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11).
@@ -84,6 +88,7 @@ __device__ __forceinline__ void mk_store4(O* row, int ox, int W, const bool* on)
 
 template <typename T, typename O>
 __global__ __launch_bounds__(256) void process_mask_kernel(MaskArgs a) {
+  constexpr bool BITS = sizeof(O) == 8;  // O = uint64_t: bit planes, one word per tile row
   __shared__ float s_src[MK_SRC];
   __shared__ float s_cf[MK_NM];
   const int b = blockIdx.z, slot = blockIdx.y;
@@ -93,7 +98,8 @@ __global__ __launch_bounds__(256) void process_mask_kernel(MaskArgs a) {
   const int oy0 = ty * MK_TH, ox0 = tx * MK_TW;
   const int oy1 = min(oy0 + MK_TH, a.out_h) - 1, ox1 = min(ox0 + MK_TW, a.out_w) - 1;  // last row / column, inclusive
   const int64_t ds = (int64_t)b * a.max_det + slot;
-  O* plane = reinterpret_cast<O*>(a.out) + (a.row_offset[b] + slot) * ((int64_t)a.out_h * a.out_w);
+  const int64_t pitch = BITS ? a.tiles_x : a.out_w;  // elements of O per output row
+  O* plane = reinterpret_cast<O*>(a.out) + (a.row_offset[b] + slot) * ((int64_t)a.out_h * pitch);
 
   const float* dr = a.det + (int64_t)b * a.det_stride + (int64_t)slot * a.det_row;
   float x1, y1, x2, y2;
@@ -116,6 +122,10 @@ __global__ __launch_bounds__(256) void process_mask_kernel(MaskArgs a) {
               float(a.top + ry0) < y2;
   const int cg = (tid & 15) * 4, r0 = tid >> 4;  // this thread's 4 columns and first row within the tile
   if (!touched) {  // a NaN box lands here too: its indicator is false everywhere
+    if constexpr (BITS) {
+      if (tid < MK_TH && oy0 + tid <= oy1) plane[(int64_t)(oy0 + tid) * pitch + tx] = O(0);
+      return;
+    }
     // zeros in 16-byte chunks (4 fp32 / 16 uint8 elements) where the chunk is aligned and inside the row
     constexpr int NV = 16 / int(sizeof(O)), CPR = MK_TW / NV;  // elements per chunk, chunks per tile row
     for (int c = tid; c < MK_TH * CPR; c += 256) {
@@ -184,7 +194,7 @@ __global__ __launch_bounds__(256) void process_mask_kernel(MaskArgs a) {
     w1[c] = sxr - float(j0[c]);
     w0[c] = 1.f - w1[c];
   }
-  if (ox0 + cg > ox1) return;
+  if (!BITS && ox0 + cg > ox1) return;  // (bit planes: the row's 16 lanes all take part in its word)
   for (int r = r0; r < MK_TH; r += 16) {
     const int oy = oy0 + r;
     if (oy > oy1) break;
@@ -203,7 +213,17 @@ __global__ __launch_bounds__(256) void process_mask_kernel(MaskArgs a) {
       }
       on[c] = o;
     }
-    mk_store4<O>(plane + (int64_t)oy * a.out_w, ox0 + cg, a.out_w, on);
+    if constexpr (BITS) {
+      unsigned nib = 0;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) nib |= (on[c] && ox0 + cg + c <= ox1 ? 1u : 0u) << c;
+      unsigned long long w = (unsigned long long)nib << cg;  // oy is uniform over the row's 16 lanes
+#pragma unroll
+      for (int m = 1; m < 16; m <<= 1) w |= __shfl_xor(w, m);
+      if (cg == 0) plane[(int64_t)oy * pitch + tx] = w;
+    } else {
+      mk_store4<O>(plane + (int64_t)oy * a.out_w, ox0 + cg, a.out_w, on);
+    }
   }
 }
 
@@ -224,8 +244,10 @@ extern "C" int ydbl_process_mask(const ydbl_mask_desc* d, void* stream) {
   if (d->det_stride < 0 || (d->det_stride && d->det_stride < (int64_t)d->max_det * det_row))
     return fail(YDBL_EINVAL, "process_mask: det_stride must be 0 or >= max_det * det_row");
   if (d->out_h < 1 || d->out_w < 1) return fail(YDBL_EINVAL, "process_mask: empty output");
-  if (d->out_dtype != YDBL_MASK_F32 && d->out_dtype != YDBL_MASK_U8)
-    return fail(YDBL_EINVAL, "process_mask: out_dtype must be YDBL_MASK_F32 or YDBL_MASK_U8");
+  if (d->out_dtype != YDBL_MASK_F32 && d->out_dtype != YDBL_MASK_U8 && d->out_dtype != YDBL_MASK_BITS)
+    return fail(YDBL_EINVAL, "process_mask: out_dtype must be YDBL_MASK_F32, YDBL_MASK_U8 or YDBL_MASK_BITS");
+  if (d->out_dtype == YDBL_MASK_BITS && reinterpret_cast<uintptr_t>(d->out) % 8)
+    return fail(YDBL_EINVAL, "process_mask: a YDBL_MASK_BITS output must be 8-byte aligned");
   if (d->top < 0 || d->left < 0 || d->bottom <= d->top || d->right <= d->left || d->bottom > d->proto.h ||
       d->right > d->proto.w)
     return fail(YDBL_EINVAL, "process_mask: the source window must be a non-empty part of the proto grid");
@@ -262,7 +284,10 @@ extern "C" int ydbl_process_mask(const ydbl_mask_desc* d, void* stream) {
   const dim3 grid((unsigned)tiles, (unsigned)(d->slots ? d->slots : d->max_det), (unsigned)d->proto.n);
   hipStream_t s = as_stream(stream);
   const bool h = d->proto.dtype == YDBL_F16, u8 = d->out_dtype == YDBL_MASK_U8;
-  if (h && u8) process_mask_kernel<_Float16, uint8_t><<<grid, 256, 0, s>>>(a);
+  if (d->out_dtype == YDBL_MASK_BITS) {
+    if (h) process_mask_kernel<_Float16, uint64_t><<<grid, 256, 0, s>>>(a);
+    else process_mask_kernel<float, uint64_t><<<grid, 256, 0, s>>>(a);
+  } else if (h && u8) process_mask_kernel<_Float16, uint8_t><<<grid, 256, 0, s>>>(a);
   else if (h) process_mask_kernel<_Float16, float><<<grid, 256, 0, s>>>(a);
   else if (u8) process_mask_kernel<float, uint8_t><<<grid, 256, 0, s>>>(a);
   else process_mask_kernel<float, float><<<grid, 256, 0, s>>>(a);

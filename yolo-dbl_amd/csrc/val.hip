@@ -15,6 +15,10 @@
 // One 256-thread workgroup per image.  IoU is evaluated in fp32 with the reference's operation
 // order and no FMA contraction, so it is bitwise the torch CPU value and the threshold compares
 // agree exactly.
+//
+// match_kernel is a template on where the IoU of a pair comes from: pair_iou on the boxes (ydbl_match_predictions),
+// or a given matrix iou[label][slot] (ydbl_match_iou: the mask IoUs of ydbl_mask_iou,
+// SegmentationValidator._process_batch(masks=True), U/models/yolo/segment/val.py:173-217).  The rule is one.
 #include <climits>
 
 #include "common.hpp"
@@ -30,6 +34,7 @@ struct MatchArgs {
   const float* det; const int* det_count;
   int n, max_det;
   const float* gt_box; const float* gt_cls; const int* gt_ofs;
+  const float* iou;  // MATRIX: [n_gt][max_det], row g = label g against the slots of its own image
   const float* iouv; int n_iou;
   int single_cls;
   int* min_det;  // [n_gt][n_iou]
@@ -48,6 +53,7 @@ __device__ __forceinline__ float pair_iou(const float* a, const float* b) {
   return inter / (((area_a + area_b) - inter) + 1e-7f);
 }
 
+template <bool MATRIX>
 __global__ __launch_bounds__(MATCH_THREADS) void match_kernel(MatchArgs p) {
   const int b = blockIdx.x;
   const int g0 = p.gt_ofs[b], nl = p.gt_ofs[b + 1] - g0;
@@ -67,7 +73,11 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_kernel(MatchArgs p) {
     float bi = 0.0f;
     for (int l = 0; l < nl; ++l) {
       // iou * (true_cls == pred_cls): a class mismatch contributes an IoU of exactly 0
-      const float v = p.gt_cls[g0 + l] == dc ? pair_iou(p.gt_box + (int64_t)(g0 + l) * 4, db) : 0.0f;
+      float v = 0.0f;
+      if (p.gt_cls[g0 + l] == dc) {
+        if constexpr (MATRIX) v = p.iou[(int64_t)(g0 + l) * p.max_det + d];
+        else v = pair_iou(p.gt_box + (int64_t)(g0 + l) * 4, db);
+      }
       if (best < 0 || v >= bi) { bi = v; best = l; }
     }
     int mask = 0;
@@ -240,14 +250,34 @@ extern "C" int ydbl_match_predictions(const ydbl_match_desc* d, void* stream) {
   if (d->n_iou < 1 || d->n_iou > MATCH_MAX_IOU) return fail(YDBL_EINVAL, "match: n_iou must be in [1, 32]");
   MatchArgs a;
   a.det = d->det; a.det_count = d->det_count; a.n = d->n; a.max_det = d->max_det;
-  a.gt_box = d->gt_box; a.gt_cls = d->gt_cls; a.gt_ofs = d->gt_ofs;
+  a.gt_box = d->gt_box; a.gt_cls = d->gt_cls; a.gt_ofs = d->gt_ofs; a.iou = nullptr;
   a.iouv = d->iouv; a.n_iou = d->n_iou; a.single_cls = d->single_cls;
   a.min_det = reinterpret_cast<int*>(d->workspace);
   a.best = a.min_det + (int64_t)d->n_gt * d->n_iou;
   a.valid = a.best + (int64_t)d->n * d->max_det;
   a.correct = d->correct;
-  match_kernel<<<d->n, MATCH_THREADS, 0, as_stream(stream)>>>(a);
+  match_kernel<false><<<d->n, MATCH_THREADS, 0, as_stream(stream)>>>(a);
   return check_launch("ydbl_match_predictions");
+}
+
+extern "C" int ydbl_match_iou(const ydbl_match_iou_desc* d, void* stream) {
+  if (!d) return fail(YDBL_EINVAL, "match_iou: null descriptor");
+  if (!d->det || !d->det_count || !d->gt_ofs || !d->iouv || !d->correct || !d->workspace)
+    return fail(YDBL_EINVAL, "match_iou: null buffer");
+  if (d->n < 1 || d->max_det < 1) return fail(YDBL_EINVAL, "match_iou: empty batch");
+  if (d->n_gt < 0 || (d->n_gt > 0 && (!d->iou || !d->gt_cls)))
+    return fail(YDBL_EINVAL, "match_iou: labels or IoU matrix missing");
+  if (d->n_iou < 1 || d->n_iou > MATCH_MAX_IOU) return fail(YDBL_EINVAL, "match_iou: n_iou must be in [1, 32]");
+  MatchArgs a;
+  a.det = d->det; a.det_count = d->det_count; a.n = d->n; a.max_det = d->max_det;
+  a.gt_box = nullptr; a.gt_cls = d->gt_cls; a.gt_ofs = d->gt_ofs; a.iou = d->iou;
+  a.iouv = d->iouv; a.n_iou = d->n_iou; a.single_cls = d->single_cls;
+  a.min_det = reinterpret_cast<int*>(d->workspace);
+  a.best = a.min_det + (int64_t)d->n_gt * d->n_iou;
+  a.valid = a.best + (int64_t)d->n * d->max_det;
+  a.correct = d->correct;
+  match_kernel<true><<<d->n, MATCH_THREADS, 0, as_stream(stream)>>>(a);
+  return check_launch("ydbl_match_iou");
 }
 
 extern "C" int64_t ydbl_confusion_workspace(int32_t n, int32_t max_det, int32_t n_gt) {

@@ -244,7 +244,7 @@ class DeconvDesc(C.Structure):
     _fields_ = [("x", View), ("y", View), ("w", C.c_void_p), ("bias", C.c_void_p), ("act", C.c_int32)]
 
 
-MASK_F32, MASK_U8 = 0, 1
+MASK_F32, MASK_U8, MASK_BITS = 0, 1, 2
 
 
 class MaskDesc(C.Structure):
@@ -255,6 +255,29 @@ class MaskDesc(C.Structure):
                 ("out_h", C.c_int32), ("out_w", C.c_int32), ("out_dtype", C.c_int32),
                 ("top", C.c_int32), ("left", C.c_int32), ("bottom", C.c_int32), ("right", C.c_int32),
                 ("sx", C.c_float), ("sy", C.c_float), ("crop_after", C.c_int32), ("slots", C.c_int32)]
+
+
+class GtBitsDesc(C.Structure):
+    """ydbl_gt_bits_desc: a batch's ground-truth masks (index map or planes) -> bit planes and areas."""
+    _fields_ = [("src", C.c_void_p), ("n", C.c_int32), ("gh", C.c_int32), ("gw", C.c_int32), ("overlap", C.c_int32),
+                ("gt_ofs", C.c_void_p), ("n_gt", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32),
+                ("bits", C.c_void_p), ("area", C.c_void_p)]
+
+
+class MaskIouDesc(C.Structure):
+    """ydbl_mask_iou_desc: mask IoU of every label against the detection slots of its image, on bit planes."""
+    _fields_ = [("det_bits", C.c_void_p), ("row_offset", C.c_void_p), ("count", C.c_void_p), ("n", C.c_int32),
+                ("max_det", C.c_int32), ("gt_bits", C.c_void_p), ("gt_ofs", C.c_void_p), ("area_gt", C.c_void_p),
+                ("n_gt", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32), ("iou", C.c_void_p),
+                ("inter", C.c_void_p), ("area_det", C.c_void_p)]
+
+
+class MatchIouDesc(C.Structure):
+    """ydbl_match_iou_desc: ydbl_match_predictions' rule on a given IoU matrix [n_gt][max_det]."""
+    _fields_ = [("det", C.c_void_p), ("det_count", C.c_void_p), ("n", C.c_int32), ("max_det", C.c_int32),
+                ("iou", C.c_void_p), ("gt_cls", C.c_void_p), ("gt_ofs", C.c_void_p), ("n_gt", C.c_int32),
+                ("iouv", C.c_void_p), ("n_iou", C.c_int32), ("single_cls", C.c_int32), ("correct", C.c_void_p),
+                ("workspace", C.c_void_p)]
 
 
 # name -> (argtypes, restype); every entry must exist in include/ydbl.h
@@ -330,6 +353,9 @@ SIGNATURES = {
     "ydbl_detect_loss_grad": ([C.POINTER(LossGradDesc), _P], C.c_int),
     "ydbl_deconv2x2_nhwc": ([C.POINTER(DeconvDesc), _P], C.c_int),
     "ydbl_process_mask": ([C.POINTER(MaskDesc), _P], C.c_int),
+    "ydbl_gt_mask_bits": ([C.POINTER(GtBitsDesc), _P], C.c_int),
+    "ydbl_mask_iou": ([C.POINTER(MaskIouDesc), _P], C.c_int),
+    "ydbl_match_iou": ([C.POINTER(MatchIouDesc), _P], C.c_int),
     "ydbl_last_error": ([], C.c_char_p),
     "ydbl_version": ([], C.c_char_p),
 }

@@ -147,6 +147,29 @@ def _segments2boxes(segments) -> np.ndarray:
 def verify_image_label(im_file: str, lb_file: str, num_cls: int):
     """U/data/utils.py:97-165 for detect labels -> (hw, lb float32 [n, 5] cls+xywhn, msg) or (None, None, msg)
     for a corrupt pair.  A missing or empty label file is a background image (0 labels)."""
+    shape, lb, _, msg = _verify_pair(im_file, lb_file, num_cls)
+    return shape, lb, msg
+
+
+def verify_image_segments(im_file: str, lb_file: str, num_cls: int):
+    """verify_image_label that keeps each row's polygon too (U/data/utils.py:127-131, :149): -> (hw, lb, segments,
+    msg), segments a list of float32 [k, 2] normalized xy, one per row of lb (in lb's order, also after duplicate
+    rows are removed).  A file without a polygon row gives every label an empty polygon -- an empty mask, as in the
+    reference; in a file with one, every row is read as a polygon (a box row as its two points)."""
+    return _verify_pair(im_file, lb_file, num_cls)
+
+
+def split_has_segments(img_path) -> bool:
+    """Whether at least one label file of the split holds a polygon row (more than 6 columns)."""
+    for lb_file in img2label_paths(get_img_files(img_path)):
+        if os.path.isfile(lb_file):
+            with open(lb_file) as f:
+                if any(len(x.split()) > 6 for x in f.read().strip().splitlines()):
+                    return True
+    return False
+
+
+def _verify_pair(im_file: str, lb_file: str, num_cls: int):
     from PIL import Image
 
     try:
@@ -160,6 +183,7 @@ def verify_image_label(im_file: str, lb_file: str, num_cls: int):
             raise ValueError(f"invalid image format {fmt}")
         msg = ""
         lb = np.zeros((0, 5), dtype=np.float32)
+        segs = []
         if os.path.isfile(lb_file):
             with open(lb_file) as f:
                 rows = [x.split() for x in f.read().strip().splitlines() if len(x)]
@@ -180,10 +204,14 @@ def verify_image_label(im_file: str, lb_file: str, num_cls: int):
                 _, i = np.unique(lb, axis=0, return_index=True)
                 if len(i) < nl:  # duplicate rows removed (in np.unique's sorted order, like the reference)
                     lb = lb[i]
+                    if segs:
+                        segs = [segs[x] for x in i]
                     msg = f"{im_file}: {nl - len(i)} duplicate labels removed"
-        return shape, lb, msg
+        if len(segs) != len(lb):  # no polygon row in the file
+            segs = [np.zeros((0, 2), dtype=np.float32) for _ in range(len(lb))]
+        return shape, lb, segs, msg
     except Exception as e:  # noqa: BLE001 - a corrupt pair is skipped with a message (verify_image_label)
-        return None, None, f"{im_file}: ignoring corrupt image/label: {e}"
+        return None, None, None, f"{im_file}: ignoring corrupt image/label: {e}"
 
 
 def load_bgr(im_file: str) -> np.ndarray:
@@ -203,15 +231,81 @@ def load_bgr(im_file: str) -> np.ndarray:
     return np.ascontiguousarray(rgb[..., ::-1])
 
 
+# ------------------------------------------------------------------------------------- ground-truth masks
+MASK_RATIO = 4  # U/cfg/default.yaml mask_ratio
+
+
+def polygon_mask(hw, poly) -> np.ndarray:
+    """A polygon as a full-resolution uint8 0 / 1 mask [h, w], in exact integer arithmetic: the vertices are
+    truncated to int32 (as polygon2mask does, U/data/utils.py:168-188) and pixel (x, y) is set iff the lattice point
+    lies in the closed polygon -- on an edge, or inside by the even-odd rule.  Our rule, standing in for
+    cv2.fillPoly (cv2 is not a dependency); the reference's 1000-point resampling of the polygon is not done."""
+    h, w = int(hw[0]), int(hw[1])
+    out = np.zeros((h, w), dtype=np.uint8)
+    p = np.asarray(poly, dtype=np.float32).reshape(-1, 2).astype(np.int32).astype(np.int64)
+    if len(p) == 0:
+        return out
+    x0, x1 = max(int(p[:, 0].min()), 0), min(int(p[:, 0].max()), w - 1)
+    y0, y1 = max(int(p[:, 1].min()), 0), min(int(p[:, 1].max()), h - 1)
+    if x0 > x1 or y0 > y1:
+        return out
+    ys, xs = np.mgrid[y0:y1 + 1, x0:x1 + 1].astype(np.int64)
+    inside = np.zeros(ys.shape, dtype=bool)
+    edge = np.zeros(ys.shape, dtype=bool)
+    q = np.roll(p, -1, axis=0)
+    for (ax, ay), (bx, by) in zip(p.tolist(), q.tolist()):
+        cross = (bx - ax) * (ys - ay) - (by - ay) * (xs - ax)
+        edge |= ((cross == 0) & (xs >= min(ax, bx)) & (xs <= max(ax, bx)) & (ys >= min(ay, by)) & (ys <= max(ay, by)))
+        dy = by - ay
+        if dy:  # the ray to +x crosses the edge (half-open in y) right of the point
+            lhs, rhs = (xs - ax) * dy, (ys - ay) * (bx - ax)
+            inside ^= ((ay <= ys) != (by <= ys)) & ((lhs < rhs) if dy > 0 else (lhs > rhs))
+    out[y0:y1 + 1, x0:x1 + 1] = inside | edge
+    return out
+
+
+def downsample_mask(mask: np.ndarray, ratio: int = MASK_RATIO) -> np.ndarray:
+    """[h, w] 0 / 1 -> [h // 4, w // 4]: pixel (X, Y) is set iff at least 2 of the four pixels in rows
+    4Y+1..4Y+2, columns 4X+1..4X+2 are.  Our reading of cv2.resize(INTER_LINEAR) at an exact 4:1 ratio with
+    round-half-up (polygon2mask's resize), not checked against cv2."""
+    if ratio != 4:
+        raise ValueError("downsample_mask is written for mask_ratio 4")
+    h, w = mask.shape[0] // 4, mask.shape[1] // 4
+    m = mask[: h * 4, : w * 4].astype(np.int32)
+    s = m[1::4, 1::4] + m[1::4, 2::4] + m[2::4, 1::4] + m[2::4, 2::4]
+    return (s >= 2).astype(np.uint8)
+
+
+def polygons2masks_overlap(hw, polys):
+    """polygons2masks_overlap (U/data/utils.py:204-225) over polygon_mask / downsample_mask: -> (index map uint8
+    [h // 4, w // 4], order).  The labels are drawn largest (1/4-map) area first with a stable sort, label order[i]
+    as value i + 1, a later one overwriting.  More than 255 polygons do not fit the uint8 map (ValueError)."""
+    if len(polys) > 255:
+        raise ValueError(f"{len(polys)} labels in one image: the overlap index map names at most 255")
+    ms = [downsample_mask(polygon_mask(hw, p)) for p in polys]
+    out = np.zeros((int(hw[0]) // 4, int(hw[1]) // 4), dtype=np.uint8)
+    order = np.argsort(-np.array([int(m.sum()) for m in ms], dtype=np.int64), kind="stable")
+    for i, j in enumerate(order):
+        out[ms[j] != 0] = i + 1
+    return out, order
+
+
 # ------------------------------------------------------------------------------------------------ dataset
 class YOLOValDataset:
     """The val-mode YOLODataset (augment=False, pad=0.5, rect per Model.val's default, U/engine/model.py:636-637).
 
     ``labels[i]`` = {"im_file", "shape" (h, w), "cls" [n, 1], "bboxes" [n, 4] normalized xywh}, in the
-    rect order; iterating yields host batches (see ``batches``)."""
+    rect order; iterating yields host batches (see ``batches``).
+
+    masks=True (segmentation validation, U/data/dataset.py:174-230 with use_segments): each label keeps its polygon
+    ("segments"), an item's polygons go through the same resize + letterbox offsets as its boxes and become the
+    overlap index map at a quarter of the letterboxed size (polygons2masks_overlap), ``cls`` / ``bboxes`` are
+    reordered to the map's order (Format._format_segments, U/data/augment.py:2078-2094) and the batches carry
+    "masks".  With masks=False nothing of this exists."""
 
     def __init__(self, img_path, imgsz=640, batch_size=16, stride=32, rect=True, pad=0.5, single_cls=False,
-                 classes=None, num_cls=80, workers=8):
+                 classes=None, num_cls=80, workers=8, masks=False):
+        self.masks = bool(masks)
         self.imgsz, self.batch_size, self.stride = int(imgsz), int(batch_size), int(stride)
         self.rect, self.pad, self.workers = bool(rect), float(pad), max(1, int(workers))
         im_files = get_img_files(img_path)
@@ -219,12 +313,18 @@ class YOLOValDataset:
         self.msgs = []
         labels = []
         with ThreadPoolExecutor(self.workers) as ex:
-            res = list(ex.map(lambda a: verify_image_label(*a, num_cls), zip(im_files, lb_files)))
-        for f, (shape, lb, msg) in zip(im_files, res):
+            if self.masks:
+                res = list(ex.map(lambda a: verify_image_segments(*a, num_cls), zip(im_files, lb_files)))
+            else:
+                res = [(sh, lb, None, msg) for sh, lb, msg in
+                       ex.map(lambda a: verify_image_label(*a, num_cls), zip(im_files, lb_files))]
+        for f, (shape, lb, segs, msg) in zip(im_files, res):
             if msg:
                 self.msgs.append(msg)
             if shape is not None:
                 labels.append({"im_file": f, "shape": shape, "cls": lb[:, 0:1], "bboxes": lb[:, 1:]})
+                if self.masks:
+                    labels[-1]["segments"] = segs
         if not labels:
             raise FileNotFoundError(f"no valid images in {img_path}")
         if classes is not None:  # update_labels (U/data/base.py:132-149)
@@ -232,6 +332,8 @@ class YOLOValDataset:
             for lb in labels:
                 j = (lb["cls"] == keep).any(1)
                 lb["cls"], lb["bboxes"] = lb["cls"][j], lb["bboxes"][j]
+                if self.masks:
+                    lb["segments"] = [sg for sg, k in zip(lb["segments"], j) if k]
         if single_cls:
             for lb in labels:
                 lb["cls"][:, 0] = 0
@@ -308,15 +410,28 @@ class YOLOValDataset:
             box[:, 3] = xyxy[:, 3] - xyxy[:, 1]
             box[:, [0, 2]] /= np.float32(W)
             box[:, [1, 3]] /= np.float32(H)
-        return {"im_file": lb["im_file"], "img": im, "ori_shape": ori, "resized_shape": (h, w), "shape": (H, W),
+        item = {"im_file": lb["im_file"], "img": im, "ori_shape": ori, "resized_shape": (h, w), "shape": (H, W),
                 "top_left": (top, left), "ratio_pad": ((h / ori[0], w / ori[1]), (left, top)),
                 "cls": lb["cls"].astype(np.float32), "bboxes": box}
+        if self.masks:
+            polys = []
+            for sg in lb["segments"]:  # Instances.denormalize / add_padding on the segments, as on the boxes
+                sg = sg.astype(np.float32).copy()
+                sg[:, 0] *= w
+                sg[:, 1] *= h
+                sg[:, 0] += left
+                sg[:, 1] += top
+                polys.append(sg)
+            item["masks"], order = polygons2masks_overlap((H, W), polys)
+            item["cls"], item["bboxes"] = item["cls"][order], item["bboxes"][order]
+        return item
 
     def batches(self):
         """Yields collated host batches: {"frames": [HWC uint8 BGR], "meta" int32 [b, 6] (h0, w0, h, w, top,
         left) for ydbl_letterbox, "shape" (H, W), "ori_shape", "ratio_pad", "im_file", "cls" [N], "bboxes" [N, 4]
-        normalized xywh of the letterboxed image, "batch_idx" [N]}.  Images are decoded by a thread pool one batch
-        ahead of the consumer."""
+        normalized xywh of the letterboxed image, "batch_idx" [N]}; with masks=True also "masks" uint8
+        [b, H // 4, W // 4], the overlap index maps (value l + 1 = the image's l-th label).  Images are decoded by a
+        thread pool one batch ahead of the consumer."""
         n = len(self.labels)
         starts = list(range(0, n, self.batch_size))
         with ThreadPoolExecutor(self.workers) as ex, ThreadPoolExecutor(1) as ahead:
@@ -327,11 +442,16 @@ class YOLOValDataset:
             for k, s in enumerate(starts):
                 ims = nxt.result()
                 nxt = ahead.submit(decode, starts[k + 1]) if k + 1 < len(starts) else None
-                items = [self._item(s + j, im) for j, im in enumerate(ims)]
+                if self.masks:  # the rasteriser runs in the loader threads
+                    items = list(ex.map(lambda a: self._item(*a), [(s + j, im) for j, im in enumerate(ims)]))
+                else:
+                    items = [self._item(s + j, im) for j, im in enumerate(ims)]
                 shapes = {it["shape"] for it in items}
                 if len(shapes) != 1:
                     raise RuntimeError(f"images of one batch letterbox to different shapes {sorted(shapes)}")
+                extra = {"masks": np.stack([it["masks"] for it in items])} if self.masks else {}
                 yield {
+                    **extra,
                     "frames": [it["img"] for it in items],
                     "meta": np.array([[*it["ori_shape"], *it["resized_shape"], *it["top_left"]] for it in items],
                                      dtype=np.int32),

@@ -745,8 +745,13 @@ class Model:
         the letterboxed-space labels): ``metrics.val_loss`` = (box, cls, dfl) averaged over the batches
         (U/engine/validator.py:185, :205), ``val/box_loss`` / ``val/cls_loss`` / ``val/dfl_loss`` in
         ``metrics.results_dict``, ``validator.image_loss`` [images, 3] in dataset order and, with save_dir,
-        val_loss.csv.  Not with augment=True (ValueError).  With the default nothing new is compiled or launched."""
-        from .validator import DetectionValidator
+        val_loss.csv.  Not with augment=True (ValueError).  With the default nothing new is compiled or launched.
+        A segmentation model whose batches carry ground-truth ``"masks"`` is scored on its masks too
+        (ydbl.engine.validator.SegmentationValidator, U/models/yolo/segment/val.py): the result is SegmentMetrics
+        (``box`` and ``seg``), ``validator.stats["tp_m"]`` the mask TP matrix.  overlap_mask=True (the default, as
+        the reference's): ``"masks"`` is the uint8 index map [B, gh, gw]; False: planes [N, gh, gw] in label order.
+        Without masks such a model is scored on its boxes, with a warning."""
+        from .validator import DetectionValidator, SegmentationValidator
 
         args = {**DEFAULTS, "conf": 0.001, "iou": 0.7, "batch": 16, "rect": True, "split": "val", "plots": True,
                 "save_json": False, "save_txt": False, "save_conf": False, "save_dir": None, **kwargs,
@@ -757,10 +762,41 @@ class Model:
             from ..nn.tasks import check_e2e_loss
 
             check_e2e_loss(self.model)  # an end2end model's criterion is E2EDetectLoss: before any device work
+        with_masks = False
         if self.model.segment:
-            _warn_seg_val()
-        self.validator = DetectionValidator(self, args)  # kept: its per-image stats (tp, conf, pred_cls, target_cls)
+            data, with_masks = _has_gt_masks(data, args["split"], len(self.model.names))
+            if not with_masks:
+                _warn_seg_val()
+            elif args.get("gather_rows") is not None:
+                raise ValueError("mask metrics are not implemented for the batch-sharded predictor (gather_rows)")
+        # kept: its per-image stats (tp, conf, pred_cls, target_cls; tp_m with mask metrics)
+        self.validator = (SegmentationValidator if with_masks else DetectionValidator)(self, args)
         return self.validator(data)
+
+
+def _has_gt_masks(data, split="val", n_names=0):
+    """(data, whether val() computes mask metrics on it): an iterable of in-memory batches does when its first batch
+    carries "masks" (the iterable is handed back with that batch in place); a dataset does when at least one label
+    file of the split holds a polygon row."""
+    import itertools
+    import os
+
+    if data is None:
+        return data, False
+    if isinstance(data, (str, os.PathLike, dict)):
+        from .dataset import split_has_segments
+        from .validator import val_source
+
+        return data, split_has_segments(val_source(data, split, n_names)[0])
+    if isinstance(data, (list, tuple)):  # known up front: said before any device work
+        has = [isinstance(b, dict) and "masks" in b for b in data]
+        if any(has) and not all(has):
+            raise ValueError("val(): only some batches carry 'masks'; mask metrics need them in every batch")
+    it = iter(data)
+    first = next(it, None)
+    if first is None:
+        return [], False
+    return itertools.chain([first], it), isinstance(first, dict) and "masks" in first
 
 
 _SEG_VAL_WARNED = False

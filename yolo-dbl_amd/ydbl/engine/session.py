@@ -594,6 +594,34 @@ class DetectSession(BatchSession):
                                 keep_idx=part.keep_idx, mc=mcv, nc=self.nc if part.multi_label else 0, slots=slots)
         return out, offs
 
+    def masks_bits(self, counts):
+        """masks() as bit planes (YDBL_MASK_BITS, include/ydbl.h): the same 0 / 1 values, 64 columns to a word, 1/32
+        of the fp32 bytes -- what ydbl_mask_iou reads.  One ydbl_process_mask launch per sub-batch plan on the current
+        stream, under masks()' conditions.  -> (words int64 [sum(counts), h, ceil(w / 64)], offsets [B + 1]); bit j
+        of word q of a row is column 64 q + j, bits past w are 0."""
+        from ..utils.ops import launch_process_mask
+
+        if not self.segment or not self.opt.nms:
+            raise RuntimeError("masks_bits(): needs a Segment head and a session with nms=True")
+        offs = [0]
+        for c in counts:
+            offs.append(offs[-1] + int(c))
+        out = torch.empty((offs[-1], self.h, (self.w + 63) // 64), dtype=torch.int64, device=self.device)
+        if offs[-1] == 0:
+            return out, offs
+        row = torch.tensor(offs[:-1], dtype=torch.int64).to(self.device, non_blocking=True)
+        for part, (a, b) in zip(self.parts, self.bounds):
+            slots = max(counts[a:b])
+            if slots == 0:
+                continue
+            pv, mcv = self._mask_views(part)
+            launch_process_mask(pv, self.det[a:b], self.count[a:b], row[a:b], out, (self.h, self.w),
+                                window=(0, 0, pv.h, pv.w), sx=_f32(pv.w / self.w), sy=_f32(pv.h / self.h),
+                                crop_after=False, max_det=self.max_det, det_stride=self.det.stride(0),
+                                keep_idx=part.keep_idx, mc=mcv, nc=self.nc if part.multi_label else 0, slots=slots,
+                                out_dtype=_lib.MASK_BITS)
+        return out, offs
+
     def masks_native(self, i, boxes, shape, dtype=torch.float32):
         """process_mask_native of image i of the last launch (retina_masks, predict.py:53-55): boxes [k, >= 4] fp32 on
         the device, already scaled to `shape` = the original image's (h, w), row j the session's j-th kept detection

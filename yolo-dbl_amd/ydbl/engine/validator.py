@@ -35,6 +35,10 @@ batches,
 [images, 3] per-image table in dataset order (each batch's rows add up to that batch's values) and, with
 ``save_dir``, ``val_loss.csv`` holds both.  Without the flag none of this exists: nothing is compiled, launched,
 copied or synchronised for it.
+
+A segmentation model whose batches carry ground-truth ``"masks"`` (or whose dataset has polygon labels) is scored by
+SegmentationValidator below: the same run plus the mask TP matrix ``stats["tp_m"]``, matched on the device on bit
+planes, and SegmentMetrics.
 """
 
 from __future__ import annotations
@@ -50,7 +54,7 @@ import torch
 
 from .. import _lib
 from ..utils.metrics import (COCO_AREA_RNG, COCO_IOU_THRS, COCO_MAX_DETS, IOUV, LOGGER, ConfusionMatrix, DetMetrics,
-                             coco_summary_lines)
+                             SegmentMetrics, coco_summary_lines)
 from .model import load_tensor_source, select_device
 
 
@@ -125,6 +129,33 @@ def match_batch(det: torch.Tensor, count: torch.Tensor, gt_box: torch.Tensor, gt
     return out.bool()
 
 
+def match_iou_batch(det: torch.Tensor, count: torch.Tensor, iou: torch.Tensor, gt_cls: torch.Tensor,
+                    gt_ofs: torch.Tensor, iouv: torch.Tensor = IOUV, single_cls: bool = False) -> torch.Tensor:
+    """match_batch on a given IoU matrix (ydbl_match_iou): iou fp32 [n_gt, max_det] on the device, row g = label g
+    (grouped order, gt_cls / gt_ofs as group_labels returns them) against the slots of its own image -- what
+    ydbl_mask_iou writes.  det supplies the class column.  Returns bool [B, max_det, len(iouv)]; same results as
+    SegmentationValidator._process_batch(masks=True) (U/models/yolo/segment/val.py:173-217) per image."""
+    if det.device.type != "cuda":
+        raise RuntimeError("match_iou_batch runs on the GPU (ydbl_match_iou); got a CPU tensor")
+    dev = det.device
+    b, max_det = det.shape[0], det.shape[1]
+    n_gt = int(gt_cls.numel())
+    if tuple(iou.shape) != (n_gt, max_det):
+        raise ValueError(f"iou must be [{n_gt}, {max_det}], got {tuple(iou.shape)}")
+    iouv_d = iouv.float().to(dev).contiguous()
+    det = det.float().contiguous()
+    iou = iou.float().contiguous()
+    count = count.to(dev, torch.int32).contiguous()
+    out = torch.empty((b, max_det, len(iouv)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(int(_lib.lib.ydbl_match_workspace(b, max_det, n_gt, len(iouv))), dtype=torch.uint8, device=dev)
+    d = _lib.MatchIouDesc(det.data_ptr(), count.data_ptr(), b, max_det, iou.data_ptr() if n_gt else None,
+                          gt_cls.data_ptr() if n_gt else None, gt_ofs.data_ptr(), n_gt, iouv_d.data_ptr(), len(iouv),
+                          int(bool(single_cls)), out.data_ptr(), ws.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(_lib.lib.ydbl_match_iou(C.byref(d), stream), "ydbl_match_iou")
+    return out.bool()
+
+
 def coco_batch(det: torch.Tensor, count: torch.Tensor, gt_box, gt_cls, batch_idx, nc: int, single_cls: bool = False,
                grouped=None, iou_thrs=COCO_IOU_THRS, area_rng=COCO_AREA_RNG, max_dets: int = COCO_MAX_DETS[-1]) -> dict:
     """COCO-protocol matching of one batch on the device (ydbl_coco_match): one launch for COCOeval.evaluateImg over
@@ -176,7 +207,26 @@ def coco_host_record(det, out, gt_cls, nc: int, single_cls: bool) -> dict:
             "ignored": out["ignored"].numpy(), "gt_cls": gcls, "gt_ignore": out["gt_ignore"].numpy().astype(bool)}
 
 
+def val_source(data, split: str, n_names: int):
+    """What a dataset-backed val() reads: (image source of the split, class count) from a data YAML / its folder /
+    its parsed dict, or the image directory / *.txt list itself."""
+    from .dataset import check_det_dataset
+
+    is_yaml = isinstance(data, dict) or str(data).rsplit(".", 1)[-1] in {"yaml", "yml"} or (
+        Path(data).is_dir() and (list(Path(data).glob("*.yaml")) or not _has_images(Path(data))))
+    if not is_yaml:
+        return data, n_names
+    info = check_det_dataset(data)
+    src = info.get(split)
+    if not src:
+        raise FileNotFoundError(f"dataset has no '{split}' split")
+    return src, info["nc"]
+
+
 class DetectionValidator:
+    stat_keys = ("tp", "conf", "pred_cls", "target_cls")
+    with_masks = False
+
     def __init__(self, model, args):
         self.model = model
         self.args = args
@@ -187,7 +237,7 @@ class DetectionValidator:
         if data is None:
             raise ValueError("val(data=...) needs a data YAML, an image folder, or an iterable of batches")
         dev = select_device(self.args.get("device"))
-        self.stats = {"tp": [], "conf": [], "pred_cls": [], "target_cls": []}
+        self.stats = {k: [] for k in self.stat_keys}
         self.target_img = []  # per image with labels or predictions: its distinct label classes (val.py:139)
         self.seen = 0
         self.nc = len(self.model.names)
@@ -203,13 +253,14 @@ class DetectionValidator:
         else:
             for batch in data:
                 self._run_tensor_batch(batch, dev)
-        st = {k: torch.cat(v, 0).numpy() if v else np.zeros((0, 10) if k == "tp" else 0) for k, v in self.stats.items()}
+        st = {k: torch.cat(v, 0).numpy() if v else np.zeros((0, 10) if k in ("tp", "tp_m") else 0)
+              for k, v in self.stats.items()}
         # get_stats (val.py:179-187)
         self.nt_per_class = np.bincount(st["target_cls"].astype(int), minlength=self.nc)
         timg = torch.cat(self.target_img).numpy() if self.target_img else np.zeros(0)
         self.nt_per_image = np.bincount(timg.astype(int), minlength=self.nc)
         if len(st["tp"]) and st["tp"].any():
-            self.metrics.process(st["tp"], st["conf"], st["pred_cls"], st["target_cls"])
+            self.metrics.process(*(st[k] for k in self.stat_keys))
         self.metrics.confusion_matrix = self.confusion_matrix  # finalize_metrics (val.py:174-177)
         if self.args.get("coco_eval"):
             self._finish_coco()
@@ -311,7 +362,15 @@ class DetectionValidator:
                                   **({"loss": {"max_labels": a["max_labels"]} if a.get("max_labels") else True}
                                      if a.get("loss") else {}))
 
+    def _match_masks(self, det_d, cnt_d, grouped, bidx, single):
+        """The mask TP matrix of the batch on the device, launched behind the box matching; None here: the
+        SegmentationValidator's step."""
+        return None
+
     def _run_tensor_batch(self, batch, dev):
+        if not self.with_masks and "masks" in batch and getattr(self.model.model, "segment", False):
+            raise ValueError("val(): only some batches carry 'masks' (the first one does not); mask metrics need "
+                             "them in every batch")
         im = load_tensor_source(batch["img"], int(self.model.model.stride.max())).to(dev).float()
         b, _, h, w = im.shape
         gt = self._loss_labels(batch["batch_idx"], batch["cls"], batch["bboxes"], b, None, xywh=False)
@@ -322,29 +381,18 @@ class DetectionValidator:
 
     def _run_dataset(self, data, dev):
         """A YOLO-format dataset: rect batches letterboxed on the GPU, predictions and labels in native space."""
-        from .dataset import YOLOValDataset, check_det_dataset
+        from .dataset import YOLOValDataset
         from .preprocess import letterbox_frames
 
         a = self.args
         stride = int(self.model.model.stride.max())
-        names = self.model.names
-        src = data
-        is_yaml = isinstance(data, dict) or str(data).rsplit(".", 1)[-1] in {"yaml", "yml"} or (
-            Path(data).is_dir() and (list(Path(data).glob("*.yaml")) or not _has_images(Path(data))))
-        if is_yaml:
-            info = check_det_dataset(data)
-            src = info.get(a.get("split", "val"))
-            if not src:
-                raise FileNotFoundError(f"dataset has no '{a.get('split', 'val')}' split")
-            num_cls = info["nc"]
-        else:
-            num_cls = len(names)
+        src, num_cls = val_source(data, a.get("split", "val"), len(self.model.names))
         imgsz = a.get("imgsz", 640)
         imgsz = imgsz if isinstance(imgsz, int) else max(imgsz)
         imgsz = max(math.ceil(imgsz / stride) * stride, stride)  # check_imgsz (U/utils/checks.py)
         ds = YOLOValDataset(src, imgsz=imgsz, batch_size=a.get("batch", 16), stride=stride, rect=a.get("rect", True),
                             single_cls=a.get("single_cls", False), classes=a.get("classes"), num_cls=num_cls,
-                            workers=a.get("workers", 8))
+                            workers=a.get("workers", 8), **({"masks": True} if self.with_masks else {}))
         self.dataset = ds
         for hb in ds.batches():
             H, W = hb["shape"]
@@ -352,6 +400,8 @@ class DetectionValidator:
             im = letterbox_frames(hb["frames"], hb["meta"], H, W, device=dev)
             # the reference's val NMS does not clip: scale_boxes clips to the original image afterwards
             gt = self._loss_labels(hb["batch_idx"], hb["cls"], hb["bboxes"], b, (W, H, W, H), xywh=True)
+            if self.with_masks:
+                self._gt_masks = hb["masks"]
             if gt is not None:
                 self.__dict__.setdefault("loss_files", []).extend(str(f) for f in hb["im_file"])
             det_d, cnt_d = self._launch(self._session(b, H, W, dev, clip=False), im, gt)
@@ -373,12 +423,15 @@ class DetectionValidator:
         single = bool(self.args.get("single_cls", False))
         grouped = group_labels(box_all, cls_all, bidx, b, det_d.device)
         tp_all = match_batch(det_d, cnt_d, box_all, cls_all, bidx, self.iouv, single, grouped=grouped)
+        tp_m_all = self._match_masks(det_d, cnt_d, grouped, bidx, single)
         if self.args.get("plots", True):  # val.py:144-145, :158-159
             confusion_batch(det_d, cnt_d, box_all, cls_all, bidx, self.confusion_matrix, single, grouped=grouped)
         coco = None
         if self.args.get("coco_eval"):
             coco = coco_batch(det_d, cnt_d, box_all, cls_all, bidx, self.nc, single, grouped=grouped)
         tp_all = tp_all.cpu()
+        if tp_m_all is not None:
+            tp_m_all = tp_m_all.cpu()  # with the box matrix: the batch's one read-back
         det, cnt = det_d.cpu(), cnt_d.cpu().tolist()
         if coco is not None:
             coco = {k: v.cpu() for k, v in coco.items()}
@@ -394,6 +447,8 @@ class DetectionValidator:
             if npr == 0:
                 if nl:
                     self.stats["tp"].append(torch.zeros(0, len(self.iouv), dtype=torch.bool))
+                    if tp_m_all is not None:  # segment/val.py:115-118: the (0, n_iou) block
+                        self.stats["tp_m"].append(torch.zeros(0, len(self.iouv), dtype=torch.bool))
                     self.stats["conf"].append(torch.zeros(0))
                     self.stats["pred_cls"].append(torch.zeros(0))
                     self.stats["target_cls"].append(cls)
@@ -402,6 +457,8 @@ class DetectionValidator:
             if single:
                 pred[:, 5] = 0
             self.stats["tp"].append(tp_all[si, :npr])
+            if tp_m_all is not None:
+                self.stats["tp_m"].append(tp_m_all[si, :npr])
             self.stats["conf"].append(pred[:, 4])
             self.stats["pred_cls"].append(pred[:, 5])
             self.stats["target_cls"].append(cls)
@@ -411,6 +468,82 @@ class DetectionValidator:
             if save and self.args.get("save_txt"):
                 save_one_txt(pred, bool(self.args.get("save_conf", False)), ori_shapes[si], self.model.names,
                              self.save_dir / "labels" / f"{Path(im_files[si]).stem}.txt")
+
+
+class SegmentationValidator(DetectionValidator):
+    """SegmentationValidator (U/models/yolo/segment/val.py): the detection validator plus the mask TP matrix
+    ``stats["tp_m"]`` and SegmentMetrics.  Reached by Model.val when the model has a Segment head and ground-truth
+    masks are supplied: tensor batches carry ``"masks"`` -- with overlap_mask=True (the default) the uint8 index map
+    [B, gh, gw] in which value l + 1 marks the pixels of the image's l-th label (labels in the order the indices
+    name, at most 255 per image), with overlap_mask=False planes [N, gh, gw] in label order; (gh, gw) normally a
+    quarter of the image (mask_ratio 4).
+
+    Per batch, right behind the box matching on the same stream and before the session runs again: the session's
+    detections as bit planes at the image size (session.masks_bits = process_mask(upsample=True), val.py:93-97),
+    the labels' masks resampled to that size as bit planes (ydbl_gt_mask_bits, val.py:204-212), their IoU by
+    popcount (ydbl_mask_iou, val.py:213) and ydbl_match_iou (val.py:217).  Nothing of it is read back but the
+    [B, max_det, n_iou] matrix, together with the box one.  The planes are addressed by slot (image b's at
+    b * max_det), so no count is needed on the host before the launches; slots past an image's count are never
+    written or read.  coco_eval, the confusion matrix, save_json / save_txt and loss stay box-based."""
+
+    stat_keys = ("tp", "tp_m", "conf", "pred_cls", "target_cls")
+    with_masks = True
+
+    def __init__(self, model, args):
+        super().__init__(model, args)
+        self.metrics = SegmentMetrics(names=model.names)
+        self.overlap = bool(args.get("overlap_mask", True))
+        if args.get("save_json") or args.get("save_txt"):
+            LOGGER.info("val() with mask metrics: save_json / save_txt write the box forms only (RLE needs "
+                        "pycocotools, polygons need cv2)")
+
+    def _launch(self, s, im, gt):
+        self._sess = s  # the mask step reads its proto / coefficient buffers and det / count / keep_idx in place
+        return super()._launch(s, im, gt)
+
+    def _run_dataset(self, data, dev):
+        if not self.overlap:
+            raise ValueError("overlap_mask=False is for tensor batches: a dataset-backed val() builds the overlap "
+                             "index map")
+        super()._run_dataset(data, dev)
+
+    def _run_tensor_batch(self, batch, dev):
+        if "masks" not in batch:
+            raise ValueError("val() with mask metrics: every batch must carry 'masks' (only some of them do)")
+        self._gt_masks = batch["masks"]
+        super()._run_tensor_batch(batch, dev)
+
+    def _match_masks(self, det_d, cnt_d, grouped, bidx, single):
+        from ..utils.ops import gt_mask_bits, mask_iou_bits
+
+        s, dev = self._sess, det_d.device
+        b, max_det = det_d.shape[0], det_d.shape[1]
+        _, cls, ofs, n_gt = grouped
+        m = torch.as_tensor(self._gt_masks)
+        if m.dim() != 3:
+            raise ValueError(f"'masks' must be [{'B' if self.overlap else 'N'}, gh, gw], got {tuple(m.shape)}")
+        bidx = torch.as_tensor(bidx).reshape(-1).long()
+        if self.overlap:
+            if m.shape[0] != b:
+                raise ValueError(f"overlap_mask=True: 'masks' is the index map [B, gh, gw]; got {m.shape[0]} maps for "
+                                 f"{b} images")
+            if n_gt and int(torch.bincount(bidx, minlength=b).max()) > 255:
+                raise ValueError("overlap_mask=True: an index map names at most 255 labels per image")
+        else:
+            if m.shape[0] != n_gt:
+                raise ValueError(f"overlap_mask=False: 'masks' holds one plane per label; got {m.shape[0]} for {n_gt}")
+            m = m[torch.argsort(bidx, stable=True).to(m.device)]  # group_labels' order
+        m = (m if self.overlap else m != 0).to(torch.uint8).to(dev).contiguous()
+        words, _ = s.masks_bits([max_det] * b)
+        gt_bits, area = gt_mask_bits(m, ofs, n_gt, (s.h, s.w), self.overlap)
+        row = torch.arange(b, dtype=torch.int64, device=dev) * max_det
+        iou = mask_iou_bits(words, row, cnt_d.to(torch.int32), max_det, gt_bits, ofs, area, (s.h, s.w))
+        return match_iou_batch(det_d, cnt_d, iou, cls, ofs, self.iouv, single)
+
+    def get_desc(self):
+        """segment/val.py:53-69 with this fork's mAP75 column in both groups."""
+        return ("%22s" + "%11s" * 12) % ("Class", "Images", "Instances", "Box(P", "R", "mAP50", "mAP75", "mAP50-95)",
+                                         "Mask(P", "R", "mAP50", "mAP75", "mAP50-95)")
 
 
 def pred_to_json(predn: torch.Tensor, filename, class_map=None) -> list:

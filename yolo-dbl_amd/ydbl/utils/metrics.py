@@ -304,6 +304,99 @@ class DetMetrics:
         return d
 
 
+def metric_fitness(m: BoxMetric) -> float:
+    """Metric.fitness (U/utils/metrics.py:758-761) with this fork's weights, as DetMetrics.results_dict computes it:
+    0.1 * mAP50 + 0.9 * mAP50-95."""
+    return 0.1 * m.map50 + 0.9 * m.map
+
+
+def mask_iou(mask1, mask2, eps=1e-7):
+    """U/utils/metrics.py:137-153: mask1 [N, n], mask2 [M, n] flattened masks -> IoU [N, M].
+
+    CPU tensors: the reference's expression (matmul, sums, division) on any values.  CUDA tensors: the masks are
+    packed to bit planes with torch ops and ydbl_mask_iou counts popcount(AND) -- defined for 0 / 1 masks only
+    (any nonzero element counts as 1), eps = 1e-7 and n <= 2^24, where it is bitwise the reference's fp32 result."""
+    if mask1.is_cuda:
+        from .ops import mask_iou_bits, pack_mask_bits
+
+        if float(eps) != 1e-7:
+            raise ValueError("mask_iou on the device is defined for eps = 1e-7 (ydbl_mask_iou)")
+        if mask1.shape[1] != mask2.shape[1]:
+            raise ValueError(f"mask_iou: masks of {mask1.shape[1]} and {mask2.shape[1]} elements")
+        dev, (N, n), M = mask1.device, mask1.shape, mask2.shape[0]
+        if N == 0 or M == 0:
+            return torch.zeros((N, M), dtype=torch.float32, device=dev)
+        g, p = pack_mask_bits(mask1), pack_mask_bits(mask2.to(dev))
+        area = (mask1 != 0).sum(1).to(torch.int32)
+        return mask_iou_bits(p, torch.zeros(1, dtype=torch.int64, device=dev),
+                             torch.full((1,), M, dtype=torch.int32, device=dev), M, g,
+                             torch.tensor([0, N], dtype=torch.int32, device=dev), area, (1, n))
+    intersection = torch.matmul(mask1, mask2.T).clamp_(0)
+    union = (mask1.sum(1)[:, None] + mask2.sum(1)[None]) - intersection
+    return intersection / (union + eps)
+
+
+class SegmentMetrics:
+    """U/utils/metrics.py:909-1048 with this fork's mAP75 in both groups.  ``box`` and ``seg`` are BoxMetric;
+    confusion_matrix, the COCO fields and val_loss are carried as DetMetrics carries them (all box-based, as in the
+    reference)."""
+
+    keys = [*DetMetrics.keys, "metrics/precision(M)", "metrics/recall(M)", "metrics/mAP50(M)", "metrics/mAP75(M)",
+            "metrics/mAP50-95(M)"]
+    curves = [*DetMetrics.curves, "Precision-Recall(M)", "F1-Confidence(M)", "Precision-Confidence(M)",
+              "Recall-Confidence(M)"]
+    coco_stat_names = list(COCO_STAT_NAMES)
+    loss_keys = DetMetrics.loss_keys
+
+    def __init__(self, names=None):
+        self.names = names or {}
+        self.box = BoxMetric()
+        self.seg = BoxMetric()
+        self.speed = {}
+        self.task = "segment"
+        self.confusion_matrix = None
+        self.coco_stats = self.coco_eval = None
+
+    process_coco = DetMetrics.process_coco
+
+    def process(self, tp, tp_m, conf, pred_cls, target_cls):
+        """:949-985: masks first, then boxes, each through ap_per_class."""
+        self.seg.nc = len(self.names)
+        self.seg.update(ap_per_class(tp_m, conf, pred_cls, target_cls, curves=True)[2:])
+        self.box.nc = len(self.names)
+        self.box.update(ap_per_class(tp, conf, pred_cls, target_cls, curves=True)[2:])
+
+    def mean_results(self):
+        return self.box.mean_results() + self.seg.mean_results()
+
+    def class_result(self, i):
+        return self.box.class_result(i) + self.seg.class_result(i)
+
+    @property
+    def maps(self):
+        return self.box.maps + self.seg.maps
+
+    @property
+    def fitness(self):
+        return metric_fitness(self.seg) + metric_fitness(self.box)
+
+    @property
+    def ap_class_index(self):
+        return self.box.ap_class_index
+
+    @property
+    def curves_results(self):
+        return self.box.curves_results + self.seg.curves_results
+
+    @property
+    def results_dict(self):
+        d = dict(zip(self.keys + ["fitness"], self.mean_results() + [self.fitness]))
+        val_loss = self.__dict__.get("val_loss")
+        if val_loss is not None:
+            d.update(zip(self.loss_keys, val_loss))
+        return d
+
+
 class ConfusionMatrix:
     """U/utils/metrics.py:294-445 for detection, counted on the device by ydbl_confusion_matrix.
 

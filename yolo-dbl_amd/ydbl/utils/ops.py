@@ -142,9 +142,12 @@ def mask_window(mh: int, mw: int, shape, padding: bool = True) -> tuple:
 
 
 def launch_process_mask(proto, det, count, row_offset, out, out_hw, *, window, sx, sy, crop_after, max_det,
-                        det_stride=0, det_row=0, coef=None, keep_idx=None, mc=(), nc=0, slots=0, stream=None):
+                        det_stride=0, det_row=0, coef=None, keep_idx=None, mc=(), nc=0, slots=0, stream=None,
+                        out_dtype=None):
     """One ydbl_process_mask launch (include/ydbl.h).  proto: a _lib.View [n, mh, mw, nm]; det / count / row_offset /
-    out / coef / keep_idx: device tensors or raw pointers; mc: the level Views when keep_idx names the anchors."""
+    out / coef / keep_idx: device tensors or raw pointers; mc: the level Views when keep_idx names the anchors.
+    out_dtype: a _lib.MASK_* code; None takes it from `out` (float32 or uint8).  _lib.MASK_BITS writes bit planes of
+    out_h * ceil(out_w / 64) 64-bit words, for which `out` is an int64 tensor."""
     ptr = lambda t: t.data_ptr() if isinstance(t, torch.Tensor) else t  # noqa: E731
     d = _lib.MaskDesc()
     d.proto = proto
@@ -154,12 +157,77 @@ def launch_process_mask(proto, det, count, row_offset, out, out_hw, *, window, s
     d.det, d.det_stride, d.det_row, d.max_det = ptr(det), int(det_stride), int(det_row), int(max_det)
     d.count, d.coef, d.row_offset, d.out = ptr(count), ptr(coef), ptr(row_offset), ptr(out)
     d.out_h, d.out_w = int(out_hw[0]), int(out_hw[1])
-    d.out_dtype = mask_dtype_code(out.dtype) if isinstance(out, torch.Tensor) else _lib.MASK_F32
+    if out_dtype is not None:
+        d.out_dtype = int(out_dtype)
+    else:
+        d.out_dtype = mask_dtype_code(out.dtype) if isinstance(out, torch.Tensor) else _lib.MASK_F32
     d.top, d.left, d.bottom, d.right = (int(v) for v in window)
     d.sx, d.sy, d.crop_after, d.slots = float(sx), float(sy), int(bool(crop_after)), int(slots)
     if stream is None:
         stream = torch.cuda.current_stream(out.device).cuda_stream
     _lib.check(_lib.lib.ydbl_process_mask(d, stream), "ydbl_process_mask")
+
+
+def gt_mask_bits(src, gt_ofs, n_gt: int, out_hw, overlap: bool = True, stream=None):
+    """One ydbl_gt_mask_bits launch (include/ydbl.h): a batch's ground-truth masks -> bit planes at out_hw.
+    src: uint8 device tensor, the index map [B, gh, gw] (overlap: value l + 1 marks image b's l-th label) or planes
+    [n_gt, gh, gw] in grouped label order; gt_ofs: int32 [B + 1] on the device (group_labels).  -> (words int64
+    [n_gt, H, ceil(W / 64)], area int32 [n_gt]).  Equal to the reference's F.interpolate(...) > 0.5 wherever its
+    value is not within rounding of 0.5 -- always at the exact ratio 4 of mask_ratio."""
+    if not (isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.uint8 and src.dim() == 3):
+        raise ValueError("gt_mask_bits: src must be a uint8 CUDA tensor [B | n_gt, gh, gw]")
+    src = src.contiguous()
+    dev = src.device
+    H, W = int(out_hw[0]), int(out_hw[1])
+    n = gt_ofs.numel() - 1
+    if src.shape[0] != (n if overlap else n_gt):
+        raise ValueError(f"gt_mask_bits: {src.shape[0]} maps for {n if overlap else n_gt} "
+                         f"{'images' if overlap else 'labels'}")
+    bits = torch.empty((n_gt, H, (W + 63) // 64), dtype=torch.int64, device=dev)
+    area = torch.empty(n_gt, dtype=torch.int32, device=dev)
+    if n_gt == 0:
+        return bits, area
+    d = _lib.GtBitsDesc(src.data_ptr(), n, src.shape[1], src.shape[2], int(bool(overlap)), gt_ofs.data_ptr(), n_gt,
+                        H, W, bits.data_ptr(), area.data_ptr())
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(_lib.lib.ydbl_gt_mask_bits(d, stream), "ydbl_gt_mask_bits")
+    return bits, area
+
+
+def mask_iou_bits(det_bits, row_offset, count, max_det: int, gt_bits, gt_ofs, area_gt, out_hw, *, counts=False,
+                  stream=None):
+    """One ydbl_mask_iou launch (include/ydbl.h): detection bit planes (session.masks_bits) against ground-truth bit
+    planes (gt_mask_bits).  row_offset int64 [B], count int32 [B], gt_ofs int32 [B + 1] on the device.
+    -> iou fp32 [n_gt, max_det] (row g: label g against the slots of its own image; columns >= count are 0), and with
+    counts=True also (inter int32 [n_gt, max_det], area_det int32 [B, max_det])."""
+    dev = det_bits.device
+    n, n_gt = count.numel(), area_gt.numel()
+    # (a batch without labels still launches, for area_det: its empty outputs are cut from one-row buffers)
+    iou = torch.empty((max(n_gt, 1), max_det), dtype=torch.float32, device=dev)
+    inter = torch.empty((max(n_gt, 1), max_det), dtype=torch.int32, device=dev) if counts else None
+    area_det = torch.empty((n, max_det), dtype=torch.int32, device=dev) if counts else None
+    d = _lib.MaskIouDesc(det_bits.data_ptr(), row_offset.data_ptr(), count.data_ptr(), n, int(max_det),
+                         gt_bits.data_ptr() if n_gt else None, gt_ofs.data_ptr(), area_gt.data_ptr() if n_gt else None,
+                         n_gt, int(out_hw[0]), int(out_hw[1]), iou.data_ptr(),
+                         inter.data_ptr() if counts else None, area_det.data_ptr() if counts else None)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(_lib.lib.ydbl_mask_iou(d, stream), "ydbl_mask_iou")
+    return (iou[:n_gt], inter[:n_gt], area_det) if counts else iou[:n_gt]
+
+
+def pack_mask_bits(masks: torch.Tensor) -> torch.Tensor:
+    """0 / 1 masks [N, ..., W] -> int64 words [N, ..., ceil(W / 64)] in the YDBL_MASK_BITS layout (bit j of word q =
+    element 64 q + j), with torch ops on the masks' device."""
+    w = masks.shape[-1]
+    m = (masks != 0).to(torch.int64)
+    pad = (-w) % 64
+    if pad:
+        m = torch.nn.functional.pad(m, (0, pad))
+    m = m.view(*m.shape[:-1], -1, 64)
+    shifts = torch.arange(64, dtype=torch.int64, device=m.device)
+    return (m << shifts).sum(-1)  # distinct bits: the sum is the OR (bit 63 wraps to the sign bit, as intended)
 
 
 def _masks_direct(protos, masks_in, bboxes, out_hw, window, sx, sy, crop_after):
