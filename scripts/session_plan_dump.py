@@ -15,6 +15,10 @@ the shared outputs.  (On the meta device an address is the tensor's byte offset 
 is null there: no launch is fused, and the offsets still show the rows.)  --split adds the batch 5, streams=2 forms;
 --fp8 one DBL-s fp8=0.1 session with that calibration.  One line per session.
 
+--list heads: the second matrix (HEADS) instead, an end2end head (tests/golden/yolov10.json: decode_e2e + top-k) and a
+Segment head (tests/golden/yolo11-seg.json: the NMS also writes keep_idx), both scale n, nc 3, fp16 at the same size:
+tests/golden/session_plans_heads_meta.json.  --list all: both matrices in one file.
+
 The script uses only the public constructors with keywords, ``children``, ``plans`` and ``plan.steps``.
 """
 import argparse
@@ -38,7 +42,10 @@ CAND = ("cand_box", "cand_score", "cand_cls", "cand_idx", "cand_count")
 RELATIVE = {
     "ydbl_detect_decode": {"y_ref": ("top", "pred"), **{f: ("own", f) for f in CAND}},
     "ydbl_detect_decode_aug": {"y_ref": ("top", "pred"), **{f: ("own", f) for f in CAND}},
-    "ydbl_nms": {"out": ("top", "det"), "out_count": ("top", "count"), **{f: ("own", f) for f in CAND}},
+    "ydbl_detect_decode_e2e": {"y_ref": ("top", "pred"), **{f: ("own", f) for f in CAND}},
+    "ydbl_nms": {"out": ("top", "det"), "out_count": ("top", "count"), "out_idx": ("own", "keep_idx"),
+                 **{f: ("own", f) for f in CAND}},
+    "ydbl_detect_topk": {"out": ("top", "det"), "out_count": ("top", "count"), **{f: ("own", f) for f in CAND}},
     "ydbl_scale_img": {"x": ("own", "input")},
     "ydbl_global_avgpool": {"y": ("top", "out")},
 }
@@ -56,7 +63,16 @@ VARIANTS = [
     ("augment_pred", AugmentSession, dict(dtype=torch.float16, keep_pred=True)),
     ("embed", EmbedSession, dict(dtype=torch.float16, embed=[4, 9])),
 ]
-SPLIT = ("detect_fp16", "detect_fp16_val", "detect_pred_no_nms", "augment", "augment_pred", "embed")
+# the second matrix: (name, model file, session class, settings)
+HEADS = [
+    ("e2e", "yolov10n.json", DetectSession, dict(dtype=torch.float16)),
+    ("e2e_pred_no_nms", "yolov10n.json", DetectSession, dict(dtype=torch.float16, keep_pred=True, nms=False)),
+    ("e2e_classes", "yolov10n.json", DetectSession, dict(dtype=torch.float16, classes=[0, 2])),
+    ("seg", "yolo11n-seg.json", DetectSession, dict(dtype=torch.float16)),
+    ("seg_val", "yolo11n-seg.json", DetectSession, dict(dtype=torch.float16, conf=0.001, multi_label=True)),
+]
+SPLIT = ("detect_fp16", "detect_fp16_val", "detect_pred_no_nms", "augment", "augment_pred", "embed",
+         "e2e", "e2e_pred_no_nms", "seg", "seg_val")
 
 
 def _addr(v, base):
@@ -77,14 +93,15 @@ def _value(v, tp, base=None):
 
 # Optional descriptor fields appended to the C ABI after the fingerprint was recorded, each documented as "NULL =
 # the behaviour before the field existed": left out of a record while unset, so that the recorded plans stay
-# comparable; a session that sets one (a segmentation model's NMS writes out_idx) shows it.
+# comparable; a session that sets one (a segmentation model's NMS writes out_idx: it has a keep_idx, also on the meta
+# device, where the address itself is null) shows it.
 APPENDED = {"NmsDesc": ("out_idx",)}
 
 
 def _struct(d, rel):
     late = APPENDED.get(type(d).__name__, ())
     return {name: _value(getattr(d, name), tp, rel.get(name)) for name, tp in d._fields_
-            if not (name in late and not getattr(d, name))}
+            if not (name in late and not getattr(d, name) and rel.get(name) is None)}
 
 
 def plan_fingerprint(plan, top, own) -> list:
@@ -131,12 +148,20 @@ def session_fingerprint(s, names=None) -> dict:
             "plans": plans if names is None else [pack(p, names) for p in plans]}
 
 
-def dump(device="meta", split=False, fp8=None, full=False) -> dict:
-    torch.manual_seed(0)
-    model = YOLO("yolov13n_DBL.yaml", nc=3).model
+def dump(device="meta", split=False, fp8=None, full=False, which="dbl") -> dict:
+    """which: "dbl" (VARIANTS), "heads" (HEADS) or "all"."""
+    rows = []
+    if which != "heads":
+        rows += [(name, "yolov13n_DBL.yaml", cls, kw) for name, cls, kw in VARIANTS]
+    if which != "dbl":
+        rows += [(name, str(ROOT / "tests" / "golden" / cfg), cls, kw) for name, cfg, cls, kw in HEADS]
     names = None if full else []
-    out = {}
-    for name, cls, kw in VARIANTS:
+    out, models = {}, {}
+    for name, cfg, cls, kw in rows:
+        if cfg not in models:
+            torch.manual_seed(0)
+            models[cfg] = YOLO(cfg, nc=3).model
+        model = models[cfg]
         out[name] = session_fingerprint(cls(model, 2, H, W, device=device, **kw), names)
         if split and name in SPLIT:
             out[name + "_split"] = session_fingerprint(cls(model, 5, H, W, device=device, streams=2, **kw), names)
@@ -163,9 +188,11 @@ def main():
     ap.add_argument("--split", action="store_true", help="add the batch 5, streams=2 forms")
     ap.add_argument("--fp8", default=None, help="an Fp8Calibration file: add one DBL-s fp8=0.1 session")
     ap.add_argument("--full", action="store_true", help="every step's descriptors in full, not only the tail's")
+    ap.add_argument("--list", default="dbl", choices=("dbl", "heads", "all"), dest="which",
+                    help="the YOLOv13-DBL matrix, the end2end / Segment heads, or both")
     ap.add_argument("--out", default=None, help="write here instead of stdout")
     a = ap.parse_args()
-    text = format_dump(dump(a.device, a.split, a.fp8, a.full))
+    text = format_dump(dump(a.device, a.split, a.fp8, a.full, a.which))
     if a.out:
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(text)

@@ -39,6 +39,17 @@ def test_plans_equal_the_recorded_fingerprint(dump):
         assert got["sessions"][name] == fp, name
 
 
+def test_head_plans_equal_the_recorded_fingerprint(dump):
+    """The end2end (decode_e2e + top-k) and Segment (NMS with keep_idx) tails, as recorded before the tail moved into
+    ydbl/tail.py (tests/golden/session_plans_heads_meta.json: scripts/session_plan_dump.py --list heads)."""
+    want = json.loads((ROOT / "tests" / "golden" / "session_plans_heads_meta.json").read_text())
+    got = json.loads(dump.format_dump(dump.dump("meta", which="heads")))
+    assert sorted(got["sessions"]) == sorted(want["sessions"]) == sorted(name for name, *_ in dump.HEADS)
+    assert got["names"] == want["names"]
+    for name, fp in want["sessions"].items():
+        assert got["sessions"][name] == fp, name
+
+
 def _rows(t, parent):
     """(first row, rows) of `t`, a slice of `parent` along dim 0 (meta tensors have no address: storage offsets)."""
     assert t.stride() == parent.stride() and t.shape[1:] == parent.shape[1:]

@@ -12,8 +12,7 @@ the staging buffers and replayed as one graph.  DetectOptions is the one record 
 
 from __future__ import annotations
 
-import ctypes as C
-import os
+import operator
 import warnings
 import weakref
 from dataclasses import dataclass
@@ -21,8 +20,9 @@ from dataclasses import dataclass
 import torch
 
 from .. import _lib
-from .._lib import DecodeAug, DecodeDesc, NmsDesc, ScaleImgDesc, View
+from .._lib import DecodeAug, DecodeDesc, ScaleImgDesc
 from ..runtime import BranchGraphRunner, GraphRunner, Plan
+from ..tail import E2ETail, NmsTail
 
 
 SPLIT_MIN_BATCH = 4  # the benched layouts: DBL-n bs32 / DBL-s bs8, bs64 / DBL-l 1280 bs8 (bench.py --streams 2)
@@ -33,13 +33,6 @@ def default_streams(batch: int) -> int:
     layout bench.py times (DESIGN.md §5: DBL-n bs32 +3 %, DBL-s bs64 +9 %, DBL-l 1280 bs8 +8.5 % over one graph;
     3-4 branches measured slower) -- else 1 (a bs1 branch per image leaves most of the chip idle)."""
     return 2 if batch >= SPLIT_MIN_BATCH else 1
-
-
-# Score threshold from which the NMS runs one workgroup per image instead of the class-split sweep (ydbl_nms_desc
-# per_image): at predict-like thresholds every image has at most 1024 candidates (the pair-matrix path; DBL-n bs32
-# at conf 0.25: 645 at most) and the split's extra workgroups and merge cost +0.8 % of the step
-# (profiles/r05/r05_nms_per_image_ab.txt); validation's conf 0.001 keeps the split.
-PER_IMAGE_NMS_CONF = 0.1
 
 
 @dataclass(frozen=True)
@@ -144,6 +137,17 @@ def _f32(v: float) -> float:
     return torch.tensor(v, dtype=torch.float32).item()
 
 
+def _of_tail(path: str, join=None) -> property:
+    """A read-only session attribute that lives on the session's tail (ydbl.tail); join: what a split session makes
+    of its sub-batch sessions' values (else it has none)."""
+    get = operator.attrgetter(path)
+
+    def read(self):
+        return join([read(c) for c in self.children]) if join and self.children else get(self.tail)
+
+    return property(read)
+
+
 def _det_count(batch: int, max_det: int, dev):
     """det [B, max_det, 6] fp32 and count [B] int32 as views of ONE zeroed buffer (flat), so a caller keeping a batch's
     outputs past the next launch copies them in one go (predict())."""
@@ -245,11 +249,13 @@ class DetectSession(BatchSession):
     other's gaps (scripts/stream_probe.py: DBL-n bs32 +10 %, DBL-s bs64 +14 %; one two-branch graph instead of
     two graphs on two streams a further +2.5 %, scripts/graph_branch_probe.py).
 
-    sparse_box: the session runs the sparse box path (_sparse_box) -- its P3 / P4 box logits exist only
-    in the 8 x 16 tiles that hold an NMS candidate of the last batch (see feats())."""
+    ``tail`` is the detection tail behind the forward (ydbl.tail: an NmsTail, or an E2ETail behind an end2end head),
+    built by _compile(); a split session's children have one each.
+    sparse_box: the session runs the sparse box path (NmsTail.sparse_box) -- its P3 / P4 box logits exist
+    only in the 8 x 16 tiles that hold an NMS candidate of the last batch (see feats())."""
 
-    sparse_box = fused_candidates = end2end = False
-    records = loss = out_flat = None
+    end2end = False
+    records = loss = out_flat = tail = None
 
     def __init__(self, model, batch: int, h: int, w: int, *args, device="cuda", streams=1, gather_rows=None,
                  options=None, _outputs=None, _bind=None, **kw):
@@ -259,7 +265,7 @@ class DetectSession(BatchSession):
         if opt.fp8 and any(type(m).__name__ == "A2C2f" for m in model.modules()):
             raise NotImplementedError("fp8=True on a model with A2C2f: no calibration record exists for the "
                                       "area-attention blocks")
-        # an end2end head (v10Detect): the tail is a top-k, not an NMS (_compile_e2e)
+        # an end2end head (v10Detect): the tail is a top-k, not an NMS (tail.E2ETail)
         self.end2end = bool(getattr(model.model[-1], "end2end", False))
         if self.end2end and opt.fp8:
             raise NotImplementedError("fp8=True on an end2end (YOLOv10) model: no calibration record exists for the "
@@ -317,8 +323,6 @@ class DetectSession(BatchSession):
         self._build()
         if self.children:
             self.A = self.children[0].A
-            self.fused_candidates = all(c.fused_candidates for c in self.children)
-            self.sparse_box = all(c.sparse_box for c in self.children)
         if _bind is None:
             own = torch.tensor([p.compiled.input.data_ptr() for p in self.parts], dtype=torch.int64)
             self.bind_ptrs.copy_(own.expand(3, -1))
@@ -351,98 +355,18 @@ class DetectSession(BatchSession):
         self.A = sum(lv.h * lv.w for lv in cm.levels)
         if self.det is None:
             self._alloc_outputs(self.A)
-        if self.end2end:
-            return self._compile_e2e(cm, plan)
-        self._init_tail(plan, self.A)
-        dd = self._decode_desc(cm.levels)
-        # No decode pass when every level's class conv is the tail of a DWConv -> Conv1x1 launch (DBL-n, nc <= 4,
-        # fp16) and no prediction tensor is wanted: those launches emit the candidates themselves (_fuse_candidates)
-        self.fused_candidates = self.pred is None and self._fuse_candidates(plan, cm.levels, dd)
-        # The sparse box path on top of that (predict thresholds, fp16 operands only: the fp8 calibration reads
-        # feats(), and below PER_IMAGE_NMS_CONF most tiles hold a candidate): _sparse_box
-        self.sparse_box = bool(opt.loss is None and self.fused_candidates and opt.nms and not self.fp8
-                               and self.conf >= PER_IMAGE_NMS_CONF
-                               and not os.environ.get("YDBL_NO_SPARSE_BOX") and self._sparse_box(plan, cm.levels, dd))
-        if not self.fused_candidates:
-            plan.launch("ydbl_detect_decode", dd, what="Detect.decode", keep=[dd])
-        self._emit_nms(plan)
+        head, outs = self.model.model[-1], (self.det, self.count, self.pred)
+        if self.end2end:  # (v10Detect) the tail is a top-k, not an NMS
+            tail = self.tail = E2ETail(plan, self.batch, self.A, head, opt, *outs)
+            tail.emit_decode(cm.levels)
+            tail.emit_topk(self.h, self.w)
+            return plan
+        tail = self.tail = NmsTail(plan, self.batch, self.A, head, opt, *outs, segment=self.segment)
+        dd = tail.emit_decode(cm.levels)
+        tail.emit_nms(self.h, self.w)
         if opt.loss is not None:
             self._emit_loss(plan, cm, dd, opt.loss)
         return plan
-
-    def _compile_e2e(self, cm, plan: Plan) -> Plan:
-        """The tail of an end2end head (v10Detect; U/nn/modules/head.py:120-141, :200-221 and the six-column branch of
-        non_max_suppression, U/utils/ops.py:224-228): the one2one levels decoded in multi-label mode whatever
-        opt.multi_label and nc are (cap = A * nc, xyxy boxes, score > conf, no `classes` filter), then
-        ydbl_detect_topk where the NMS stands for the other heads -- the first min(min(head.max_det, A), max_det)
-        pairs by (score, anchor * nc + class), the `classes` filter behind the cut.  iou, agnostic, max_nms and max_wh
-        play no part, as in the reference; no fused candidates, no sparse box path.  keep_pred: the dense one2one map
-        [B, 4+nc, A] with xyxy rows.  nms=False: the decode alone."""
-        from ..nn.modules import E2ETail
-
-        opt, head, dev = self.opt, cm.detect, plan.device
-        self.multi_label = True
-        classes = opt.classes
-        self.classes_t = torch.tensor(list(classes), dtype=torch.int32, device=dev) if classes is not None else None
-        tail = self.tail = E2ETail(plan, cm.levels, head.stride.tolist(), self.nc, self.batch, conf=self.conf,
-                                   k_head=min(int(head.max_det), self.A), max_det=self.max_det, det=self.det,
-                                   count=self.count, pred=self.pred, classes=self.classes_t,
-                                   clip=(self.h, self.w) if opt.clip else None,
-                                   per_image=self.conf >= PER_IMAGE_NMS_CONF, topk=bool(opt.nms))
-        self.cap = tail.cap
-        self.cand_box, self.cand_score, self.cand_cls = tail.cand_box, tail.cand_score, tail.cand_cls
-        self.cand_idx, self._cand_count = tail.cand_idx, tail.cand_count
-        return plan
-
-    # ------------------------------------------------------------------ the detection tail
-    def _init_tail(self, plan: Plan, A: int):
-        """The buffers behind the head, for A anchors per image: the candidate lists (cap = A, x nc multi-label) the
-        decode fills and the NMS reads, the ``classes`` filter and the NMS workspace, zero-filled once
-        (include/ydbl.h)."""
-        batch, dev = self.batch, plan.device
-        self.multi_label = bool(self.opt.multi_label) and self.nc > 1
-        cap = self.cap = A * self.nc if self.multi_label else A
-        self.cand_box = torch.empty((batch, cap, 4), dtype=torch.float32, device=dev)
-        self.cand_score = torch.empty((batch, cap), dtype=torch.float32, device=dev)
-        self.cand_cls = torch.empty((batch, cap), dtype=torch.int32, device=dev)
-        self.cand_idx = torch.empty((batch, cap), dtype=torch.int32, device=dev)
-        self._cand_count = torch.zeros((batch,), dtype=torch.int32, device=dev)
-        classes = self.opt.classes
-        self.classes_t = torch.tensor(list(classes), dtype=torch.int32, device=dev) if classes is not None else None
-        self._nms_ws = torch.zeros(int(_lib.lib.ydbl_nms_workspace(batch, cap, self.opt.max_nms)), dtype=torch.uint8,
-                                   device=dev)
-        self.keep_idx = None
-        if self.segment:  # per kept row the candidate's index: finds its mask coefficients (ydbl_nms_desc.out_idx)
-            self.keep_idx = torch.full((batch, self.max_det), -1, dtype=torch.int32, device=dev)
-            plan.buffers.append(self.keep_idx)
-        plan.buffers += [self.cand_box, self.cand_score, self.cand_cls, self.cand_idx, self._cand_count, self.det,
-                         self.count, self._nms_ws]
-
-    def _decode_desc(self, levels) -> DecodeDesc:
-        """The decode of one forward's levels into the candidate lists (and ``pred``)."""
-        nc, ct = self.nc, self.classes_t
-        boxes = (View * 3)(*[lv.cslice(0, 64).struct() for lv in levels])
-        clss = (View * 3)(*[lv.cslice(64, nc).struct() for lv in levels])
-        strides = (C.c_float * 3)(*[float(s) for s in self.model.model[-1].stride.tolist()])
-        return DecodeDesc(boxes, clss, len(levels), nc, strides, self.conf, int(self.multi_label),
-                          ct.data_ptr() if ct is not None else None, len(ct) if ct is not None else 0,
-                          self.pred.data_ptr() if self.pred is not None else None,
-                          self.cand_box.data_ptr(), self.cand_score.data_ptr(), self.cand_cls.data_ptr(),
-                          self.cand_idx.data_ptr(), self._cand_count.data_ptr(), self.cap)
-
-    def _emit_nms(self, plan: Plan):
-        """ydbl_nms over the candidate lists into det / count; nms=False: forward + decode only
-        (DetectionModel.forward -> (y, feats))."""
-        if not self.opt.nms:
-            return
-        opt, h, w = self.opt, self.h, self.w
-        nd = NmsDesc(self.cand_box.data_ptr(), self.cand_score.data_ptr(), self.cand_cls.data_ptr(),
-                     self.cand_idx.data_ptr(), self._cand_count.data_ptr(), self.batch, self.cap, self.iou, self.max_det,
-                     int(opt.max_nms), int(bool(opt.agnostic)), float(opt.max_wh), float(w) if opt.clip else 0.0,
-                     float(h) if opt.clip else 0.0, self.det.data_ptr(), self.count.data_ptr(), self._nms_ws.data_ptr(),
-                     self.det.stride(0), self.count.stride(0), int(self.conf >= PER_IMAGE_NMS_CONF),
-                     self.keep_idx.data_ptr() if self.keep_idx is not None else None)
-        plan.launch("ydbl_nms", nd, what="NMS", keep=[nd])
 
     def _emit_loss(self, plan: Plan, cm, dd: DecodeDesc, cfg: dict):
         """ydbl_detect_loss as the plan's last step, reading the level buffers in place: self.loss (utils.loss
@@ -465,81 +389,6 @@ class DetectSession(BatchSession):
         if tuple(gt.shape) != tuple(self.loss.gt.shape):
             raise ValueError(f"label buffer shape {tuple(gt.shape)} != {tuple(self.loss.gt.shape)}")
         self.loss.gt.copy_(gt, non_blocking=True)
-
-    @staticmethod
-    def _fuse_candidates(plan: Plan, levels, dd: DecodeDesc) -> bool:
-        """Point the candidate sinks of the plan's class-conv tail launches (include/ydbl.h, ydbl_dsconv_desc) at the
-        decode descriptor's lists.  Only when the plan is fp16 and EVERY level's class logits are written by such a
-        tail (in level order, after the level's box launch: Detect.emit); else nothing is touched and the caller
-        keeps the decode launch.  The first level's launch zeroes the counters."""
-        if plan.dtype != torch.float16:
-            return False
-        tails = {}
-        for st in plan.steps:
-            if st.fn.__name__ == "ydbl_dsconv_nhwc" and st.args[0].tail_w:
-                tails[st.args[0].tail_y.ptr] = st.args[0]
-        descs = [tails.get(dd.cls[i].ptr) for i in range(len(levels))]
-        if any(d is None for d in descs):
-            return False
-        a0 = 0
-        for i, (lv, d) in enumerate(zip(levels, descs)):
-            d.cand_box, d.cand_score, d.cand_cls = dd.cand_box, dd.cand_score, dd.cand_cls
-            d.cand_idx, d.cand_count, d.cand_cap = dd.cand_idx, dd.cand_count, dd.cap
-            d.conf_thres, d.multi_label = dd.conf_thres, dd.multi_label
-            d.classes, d.nclasses = dd.classes, dd.nclasses
-            d.level_stride, d.anchor0, d.box = dd.stride[i], a0, dd.box[i]
-            d.zero_counts = int(i == 0)
-            a0 += lv.h * lv.w
-        return True
-
-    def _sparse_box(self, plan: Plan, levels, dd: DecodeDesc) -> bool:
-        """The sparse box path (include/ydbl.h: the deferred sink of ydbl_dsconv_desc, the tile mask and candidate
-        sink of ydbl_bottleneck_desc), on the levels whose box branch is ONE ydbl_bottleneck_nhwc launch with pw = 1
-        (emit_detect_box: DBL-n P3 / P4): the level's box launch moves behind its class tail, the tail flags the
-        8 x 16 tiles that hold a candidate instead of decoding, and the box launch computes only those tiles and
-        decodes the candidates' boxes.  One mask buffer for all such levels, zeroed by the launch that zeroes the
-        counters.  The other levels (20^2: three generic convs) keep their order and today's sink.  False, with
-        nothing touched, when no level qualifies."""
-        tails, boxes = {}, {}
-        for k, st in enumerate(plan.steps):
-            name = st.fn.__name__
-            if name == "ydbl_dsconv_nhwc" and st.args[0].tail_w and st.args[0].cand_count:
-                tails[st.args[0].tail_y.ptr] = k
-            elif name == "ydbl_bottleneck_nhwc" and st.args[0].pw:
-                boxes[st.args[0].y.ptr] = k
-        picks = []
-        for i, lv in enumerate(levels):
-            kb, kt = boxes.get(dd.box[i].ptr), tails.get(dd.cls[i].ptr)
-            if kb is not None and kt is not None and kb < kt:
-                picks.append((i, kb, kt, -(-lv.w // 16), -(-lv.h // 8)))
-        if not picks:
-            return False
-        sizes = [levels[i].n * tx * ty for i, _, _, tx, ty in picks]
-        mask = torch.zeros(sum(sizes), dtype=torch.uint8, device=plan.device)
-        plan.buffers.append(mask)
-        self.tile_masks, off, after = {}, 0, {}
-        for (i, kb, kt, tx, ty), size in zip(picks, sizes):
-            self.tile_masks[i] = mask[off:off + size].view(levels[i].n, ty, tx)
-            td, bd = plan.steps[kt].args[0], plan.steps[kb].args[0]
-            td.tile_mask, td.mask_tiles_x, td.mask_tiles_img = mask.data_ptr() + off, tx, tx * ty
-            bd.tile_mask = mask.data_ptr() + off
-            bd.cand_box, bd.cand_idx, bd.cand_count, bd.cand_cap = dd.cand_box, dd.cand_idx, dd.cand_count, dd.cap
-            bd.level_stride, bd.anchor0, bd.nc, bd.multi_label = td.level_stride, td.anchor0, dd.nc, dd.multi_label
-            after[kt] = plan.steps[kb]
-            off += size
-        for st in plan.steps:  # the call that zeroes the counters zeroes the masks too
-            if st.fn.__name__ == "ydbl_dsconv_nhwc" and st.args[0].cand_count and st.args[0].zero_counts:
-                st.args[0].mask_zero, st.args[0].mask_zero_bytes = mask.data_ptr(), mask.numel()
-        moved = {id(s) for s in after.values()}
-        steps = []
-        for k, st in enumerate(plan.steps):  # class branch first, the level's box launch right behind its tail
-            if id(st) in moved:
-                continue
-            steps.append(st)
-            if k in after:
-                steps.append(after[k])
-        plan.steps = steps
-        return True
 
     # ------------------------------------------------------------------ instance masks (a Segment head)
     def seg_outputs(self):
@@ -567,46 +416,20 @@ class DetectSession(BatchSession):
 
         return one(proto), [one(v) for v in mcs]
 
-    def masks(self, counts, dtype=torch.float32):
-        """process_mask(upsample=True) of the last launch's detections (U/models/yolo/segment/predict.py:56-57): one
-        ydbl_process_mask launch per sub-batch plan on the current stream, reading the plan's proto and coefficient
-        buffers and the session's det / count / keep_idx in place -- call it before the session is launched again.
-        counts: the host copy of self.count.  -> (masks [sum(counts), h, w] 0 / 1 in `dtype`, offsets [B + 1])."""
+    def _check_masks(self, what: str):
+        if not self.segment or not self.opt.nms:
+            raise RuntimeError(f"{what}(): needs a Segment head and a session with nms=True")
+
+    def _masks(self, what: str, counts, width: int, dtype, out_dtype=None):
+        """masks() / masks_bits(): the rows' offsets and one ydbl_process_mask launch per sub-batch plan into
+        out [sum(counts), h, width] of `dtype` -> (out, offsets [B + 1])."""
         from ..utils.ops import launch_process_mask
 
-        if not self.segment or not self.opt.nms:
-            raise RuntimeError("masks(): needs a Segment head and a session with nms=True")
+        self._check_masks(what)
         offs = [0]
         for c in counts:
             offs.append(offs[-1] + int(c))
-        out = torch.empty((offs[-1], self.h, self.w), dtype=dtype, device=self.device)
-        if offs[-1] == 0:
-            return out, offs
-        row = torch.tensor(offs[:-1], dtype=torch.int64).to(self.device, non_blocking=True)
-        for part, (a, b) in zip(self.parts, self.bounds):
-            slots = max(counts[a:b])
-            if slots == 0:
-                continue
-            pv, mcv = self._mask_views(part)
-            launch_process_mask(pv, self.det[a:b], self.count[a:b], row[a:b], out, (self.h, self.w),
-                                window=(0, 0, pv.h, pv.w), sx=_f32(pv.w / self.w), sy=_f32(pv.h / self.h),
-                                crop_after=False, max_det=self.max_det, det_stride=self.det.stride(0),
-                                keep_idx=part.keep_idx, mc=mcv, nc=self.nc if part.multi_label else 0, slots=slots)
-        return out, offs
-
-    def masks_bits(self, counts):
-        """masks() as bit planes (YDBL_MASK_BITS, include/ydbl.h): the same 0 / 1 values, 64 columns to a word, 1/32
-        of the fp32 bytes -- what ydbl_mask_iou reads.  One ydbl_process_mask launch per sub-batch plan on the current
-        stream, under masks()' conditions.  -> (words int64 [sum(counts), h, ceil(w / 64)], offsets [B + 1]); bit j
-        of word q of a row is column 64 q + j, bits past w are 0."""
-        from ..utils.ops import launch_process_mask
-
-        if not self.segment or not self.opt.nms:
-            raise RuntimeError("masks_bits(): needs a Segment head and a session with nms=True")
-        offs = [0]
-        for c in counts:
-            offs.append(offs[-1] + int(c))
-        out = torch.empty((offs[-1], self.h, (self.w + 63) // 64), dtype=torch.int64, device=self.device)
+        out = torch.empty((offs[-1], self.h, width), dtype=dtype, device=self.device)
         if offs[-1] == 0:
             return out, offs
         row = torch.tensor(offs[:-1], dtype=torch.int64).to(self.device, non_blocking=True)
@@ -619,8 +442,22 @@ class DetectSession(BatchSession):
                                 window=(0, 0, pv.h, pv.w), sx=_f32(pv.w / self.w), sy=_f32(pv.h / self.h),
                                 crop_after=False, max_det=self.max_det, det_stride=self.det.stride(0),
                                 keep_idx=part.keep_idx, mc=mcv, nc=self.nc if part.multi_label else 0, slots=slots,
-                                out_dtype=_lib.MASK_BITS)
+                                out_dtype=out_dtype)
         return out, offs
+
+    def masks(self, counts, dtype=torch.float32):
+        """process_mask(upsample=True) of the last launch's detections (U/models/yolo/segment/predict.py:56-57): one
+        ydbl_process_mask launch per sub-batch plan on the current stream, reading the plan's proto and coefficient
+        buffers and the session's det / count / keep_idx in place -- call it before the session is launched again.
+        counts: the host copy of self.count.  -> (masks [sum(counts), h, w] 0 / 1 in `dtype`, offsets [B + 1])."""
+        return self._masks("masks", counts, self.w, dtype)
+
+    def masks_bits(self, counts):
+        """masks() as bit planes (YDBL_MASK_BITS, include/ydbl.h): the same 0 / 1 values, 64 columns to a word, 1/32
+        of the fp32 bytes -- what ydbl_mask_iou reads.  One ydbl_process_mask launch per sub-batch plan on the current
+        stream, under masks()' conditions.  -> (words int64 [sum(counts), h, ceil(w / 64)], offsets [B + 1]); bit j
+        of word q of a row is column 64 q + j, bits past w are 0."""
+        return self._masks("masks_bits", counts, (self.w + 63) // 64, torch.int64, _lib.MASK_BITS)
 
     def masks_native(self, i, boxes, shape, dtype=torch.float32):
         """process_mask_native of image i of the last launch (retina_masks, predict.py:53-55): boxes [k, >= 4] fp32 on
@@ -628,8 +465,7 @@ class DetectSession(BatchSession):
         of the image.  One launch on the current stream -> masks [k, shape[0], shape[1]] 0 / 1 in `dtype`."""
         from ..utils.ops import launch_process_mask, mask_window
 
-        if not self.segment or not self.opt.nms:
-            raise RuntimeError("masks_native(): needs a Segment head and a session with nms=True")
+        self._check_masks("masks_native")
         k = boxes.shape[0]
         out = torch.empty((k, int(shape[0]), int(shape[1])), dtype=dtype, device=self.device)
         if k == 0:
@@ -643,10 +479,12 @@ class DetectSession(BatchSession):
                             keep_idx=part.keep_idx[i - a], mc=mcv, nc=self.nc if part.multi_label else 0, slots=k)
         return out
 
-    @property
-    def cand_count(self):
-        """Candidates per image of the last launch (a split session's: its sub-batches' counters, concatenated)."""
-        return torch.cat([c.cand_count for c in self.children]) if self.children else self._cand_count
+    # What the tail owns, under the names it has on a session; a split session has them on its children only, except:
+    cand_box, cand_score, cand_cls, cand_idx = (_of_tail("cands." + n) for n in ("box", "score", "cls", "idx"))
+    cap, multi_label, keep_idx, tile_masks = (_of_tail(n) for n in ("cap", "multi_label", "keep_idx", "tile_masks"))
+    classes_t = _of_tail("classes")
+    cand_count = _of_tail("cands.count", torch.cat)  # candidates per image of the last launch
+    fused_candidates, sparse_box = _of_tail("fused", all), _of_tail("sparse", all)  # (true of every sub-batch plan)
 
     # ------------------------------------------------------------------ execution
     def can_bind(self, x: torch.Tensor) -> bool:
@@ -845,7 +683,7 @@ class AugmentSession(DetectSession):
     (the three passes have no single set of levels to score: ValueError from the constructor, and load_labels()
     raises RuntimeError as on any session built without loss=).  The NMS candidate capacity is A_tot (x nc
     multi-label): 15 049 at 640^2, above ydbl_nms's 8192-candidate pair-matrix limit like the plain session's 8400,
-    so its workspace per image is the same ~9.1 MB (ydbl_nms_workspace: 16384 sort slots, 8 class-group lists, 8192
+    so its workspace per image is the same ~9.1 MB (tail.nms_workspace: 16384 sort slots, 8 class-group lists, 8192
     pair-matrix rows)."""
 
     def __init__(self, model, batch: int, h: int, w: int, *args, device="cuda", streams=1, options=None,
@@ -876,7 +714,8 @@ class AugmentSession(DetectSession):
         cms = [self.model.compile(batch, hp, wp, self.dtype, device=dev) for _, _, _, (hp, wp), *_ in self.passes]
         self.compiled_passes, self.compiled = cms, cms[0]  # (load() fills pass 0's staging buffer)
         plan = Plan(dev, self.dtype)
-        self._init_tail(plan, A)
+        tail = self.tail = NmsTail(plan, batch, A, self.model.model[-1], self.opt, self.det, self.count, self.pred,
+                                   segment=self.segment)
         ch = cms[0].input.shape[1]
         for cm, (ratio, flip, (sh, sw), (hp, wp), *_) in zip(cms[1:], self.passes[1:]):
             sd = ScaleImgDesc(cms[0].input.data_ptr(), batch, ch, h, w, sh, sw, hp, wp, int(flip), SCALE_IMG_PAD,
@@ -887,10 +726,9 @@ class AugmentSession(DetectSession):
                 raise RuntimeError(f"pass {i}: the compiled levels hold {sum(lv.h * lv.w for lv in cm.levels)} "
                                    f"anchors, augment_passes() expects {A_i}")
             plan.steps += cm.plan.steps
-            dd = self._decode_desc(cm.levels)
-            ga = DecodeAug(float(ratio), float(w) if flip else 0.0, a_lo, a_hi, pos, A, int(i > 0))
-            plan.launch("ydbl_detect_decode_aug", dd, ga, what=f"Detect.decode pass {i}", keep=[dd, ga])
-        self._emit_nms(plan)
+            tail.emit_decode_aug(cm.levels, DecodeAug(float(ratio), float(w) if flip else 0.0, a_lo, a_hi, pos, A,
+                                                      int(i > 0)), i)
+        tail.emit_nms(h, w)
         return plan
 
     def can_bind(self, x) -> bool:

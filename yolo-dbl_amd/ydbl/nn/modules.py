@@ -24,7 +24,6 @@ U/nn/tasks.py:217) is folded into its pointwise conv here.
 from __future__ import annotations
 
 import copy
-import ctypes as C
 import math
 import os
 
@@ -34,6 +33,7 @@ import torch.nn as nn
 from .. import _lib
 from .._lib import ConvDesc, DwConvDesc, HgDesc, View
 from ..runtime import TV, Plan, Step, round_up, weights_signature, ydbl_env
+from ..tail import CandidateLists, E2ETail, decode_desc
 
 
 # =============================================================================== weight prep + launches
@@ -1557,15 +1557,9 @@ class Detect(PlanModule):
         A = sum(lv.h * lv.w for lv in levels)
         dev = plan.device
         pred = torch.empty((B, 4 + self.nc, A), dtype=torch.float32, device=dev)
-        cand = [torch.empty((B, A, 4), dtype=torch.float32, device=dev), torch.empty((B, A), dtype=torch.float32,
-                device=dev), torch.empty((B, A), dtype=torch.int32, device=dev),
-                torch.empty((B, A), dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev)]
-        plan.buffers += [pred, *cand]
-        boxes = (View * 3)(*[lv.cslice(0, 4 * self.reg_max).struct() for lv in levels])
-        clss = (View * 3)(*[lv.cslice(4 * self.reg_max, self.nc).struct() for lv in levels])
-        strides = (C.c_float * 3)(*[float(s) for s in self.stride.tolist()])
-        dd = _lib.DecodeDesc(boxes, clss, len(levels), self.nc, strides, 2.0, 0, None, 0, pred.data_ptr(),
-                             *[t.data_ptr() for t in cand], A)
+        plan.buffers.append(pred)
+        dd = decode_desc(levels, self.stride.tolist(), self.nc, self.reg_max, 2.0, False, None, pred,
+                         CandidateLists(B, A, dev, plan))
         plan.launch("ydbl_detect_decode", dd, what="Detect.decode", keep=[dd])
         dt = plan.dtype
         return lambda: (pred.to(dt, copy=True), [lv.nchw().contiguous() for lv in levels])
@@ -1573,7 +1567,7 @@ class Detect(PlanModule):
     def emit(self, plan, xs, out=None):
         """Per level: one NHWC buffer [B,h,w,64+nc] (box logits | class logits) = the reference's x[i].  Box branch
         first; a DetectSession on the sparse box path moves the one-launch box branch of a level behind the level's
-        class tail once it knows its thresholds (engine.session.DetectSession._sparse_box)."""
+        class tail once it knows its thresholds (tail.NmsTail.sparse_box)."""
         return self._emit_branches(plan, xs, self.cv2, self.cv3)
 
     def _emit_branches(self, plan, xs, cv2, cv3):
@@ -1645,58 +1639,20 @@ class v10Detect(Detect):  # noqa: N801 (reference name)
         (y [B, k, 6], {"one2many": [x_i], "one2one": [x_i]}) as fresh tensors of the plan's dtype."""
         if not float(self.stride.abs().sum()):
             raise RuntimeError("Detect.stride is unset: build the module through DetectionModel (stride probe)")
+        from ..engine.session import DetectOptions
+
         many = self._emit_branches(plan, xs, self.cv2, self.cv3)
         one = self.emit(plan, xs)
         B = one[0].n
         A = sum(lv.h * lv.w for lv in one)
-        tail = E2ETail(plan, one, self.stride.tolist(), self.nc, B, conf=-1.0, k_head=min(self.max_det, A),
-                       max_det=min(self.max_det, A))
+        # every (anchor, class) pair a candidate, the head's own cut, boxes unclipped
+        opt = DetectOptions(conf=-1.0, max_det=min(self.max_det, A), clip=False)
+        tail = E2ETail(plan, B, A, self, opt)
+        tail.emit_decode(one)
+        tail.emit_topk(0, 0)
         dt = plan.dtype
         return lambda: (tail.det.to(dt, copy=True), {"one2many": [lv.nchw().contiguous() for lv in many],
                                                      "one2one": [lv.nchw().contiguous() for lv in one]})
-
-
-class E2ETail:
-    """The detection tail of an end2end head behind its one2one levels, appended to `plan`: ydbl_detect_decode_e2e in
-    multi-label mode (cap = A * nc candidates per image, xyxy boxes, no `classes` filter: that one follows the cut)
-    and ydbl_detect_topk into det [B, max_det, 6] / count [B].  conf: the candidates' threshold (score > conf; -1 =
-    every pair, DetectionModel.forward); k_head = min(the head's max_det, A); det / count / pred: the caller's
-    buffers (views with their own image stride are fine), else allocated; classes: a device int32 tensor or None;
-    clip = (h, w) or None; per_image: ydbl_topk_desc's schedule; topk=False: the decode alone."""
-
-    def __init__(self, plan: Plan, levels, strides, nc, batch, conf, k_head, max_det, det=None, count=None, pred=None,
-                 classes=None, clip=None, per_image=False, topk=True):
-        dev = plan.device
-        A = sum(lv.h * lv.w for lv in levels)
-        cap = self.cap = A * nc
-        self.cand_box = torch.empty((batch, cap, 4), dtype=torch.float32, device=dev)
-        self.cand_score = torch.empty((batch, cap), dtype=torch.float32, device=dev)
-        self.cand_cls = torch.empty((batch, cap), dtype=torch.int32, device=dev)
-        self.cand_idx = torch.empty((batch, cap), dtype=torch.int32, device=dev)
-        self.cand_count = torch.zeros((batch,), dtype=torch.int32, device=dev)
-        self.det = det if det is not None else torch.zeros((batch, max_det, 6), dtype=torch.float32, device=dev)
-        self.count = count if count is not None else torch.zeros((batch,), dtype=torch.int32, device=dev)
-        nws = 16 if dev.type == "meta" else int(_lib.lib.ydbl_detect_topk_workspace(batch, cap))
-        self.ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-        plan.buffers += [self.cand_box, self.cand_score, self.cand_cls, self.cand_idx, self.cand_count, self.det,
-                         self.count, self.ws, *(t for t in (classes, pred) if t is not None)]
-        boxes = (View * 3)(*[lv.cslice(0, 64).struct() for lv in levels])
-        clss = (View * 3)(*[lv.cslice(64, nc).struct() for lv in levels])
-        st = (C.c_float * 3)(*[float(s) for s in strides])
-        self.dd = _lib.DecodeDesc(boxes, clss, len(levels), nc, st, float(conf), 1, None, 0,
-                                  pred.data_ptr() if pred is not None else None, self.cand_box.data_ptr(),
-                                  self.cand_score.data_ptr(), self.cand_cls.data_ptr(), self.cand_idx.data_ptr(),
-                                  self.cand_count.data_ptr(), cap)
-        plan.launch("ydbl_detect_decode_e2e", self.dd, what="Detect.decode e2e", keep=[self.dd])
-        if not topk:
-            return
-        self.td = _lib.TopkDesc(self.cand_box.data_ptr(), self.cand_score.data_ptr(), self.cand_cls.data_ptr(),
-                                self.cand_idx.data_ptr(), self.cand_count.data_ptr(), batch, cap, int(k_head),
-                                int(max_det), classes.data_ptr() if classes is not None else None,
-                                len(classes) if classes is not None else 0, float(clip[1]) if clip else 0.0,
-                                float(clip[0]) if clip else 0.0, self.det.data_ptr(), self.count.data_ptr(),
-                                self.det.stride(0), self.count.stride(0), self.ws.data_ptr(), nws, int(bool(per_image)))
-        plan.launch("ydbl_detect_topk", self.td, what="TopK", keep=[self.td])
 
 
 def emit_deconv2x2(plan: Plan, m: nn.ConvTranspose2d, x: TV, out: TV | None = None, act=_lib.ACT_NONE) -> TV:

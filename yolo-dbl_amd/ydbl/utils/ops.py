@@ -8,6 +8,7 @@ import torch
 
 from .. import _lib
 from .._lib import NmsDesc, PredCandDesc
+from ..tail import CandidateLists, nms_workspace
 
 
 def make_divisible(x, divisor):
@@ -91,25 +92,19 @@ def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=Non
     multi_label = bool(multi_label) and nc > 1
     pred = prediction.detach().float().contiguous()
     dev = pred.device
-    cap = A * nc if multi_label else A
-    cand_box = torch.empty((bs, cap, 4), dtype=torch.float32, device=dev)
-    cand_score = torch.empty((bs, cap), dtype=torch.float32, device=dev)
-    cand_cls = torch.empty((bs, cap), dtype=torch.int32, device=dev)
-    cand_idx = torch.empty((bs, cap), dtype=torch.int32, device=dev)
-    cand_count = torch.empty((bs,), dtype=torch.int32, device=dev)
+    cands = CandidateLists(bs, CandidateLists.capacity(A, nc, multi_label), dev)
     cls_t = torch.tensor(list(classes), dtype=torch.int32, device=dev) if classes is not None else None
     stream = torch.cuda.current_stream(dev).cuda_stream
     pd = PredCandDesc(pred.data_ptr(), bs, nc, A, float(conf_thres), int(multi_label),
                       cls_t.data_ptr() if cls_t is not None else None, len(cls_t) if cls_t is not None else 0,
-                      cand_box.data_ptr(), cand_score.data_ptr(), cand_cls.data_ptr(), cand_idx.data_ptr(),
-                      cand_count.data_ptr(), cap)
+                      **cands.fields())
     _lib.check(_lib.lib.ydbl_pred_candidates(pd, stream), "ydbl_pred_candidates")
     out = torch.zeros((bs, max_det, 6), dtype=torch.float32, device=dev)
     cnt = torch.zeros((bs,), dtype=torch.int32, device=dev)
-    ws = torch.zeros(int(_lib.lib.ydbl_nms_workspace(bs, cap, max_nms)), dtype=torch.uint8, device=dev)  # zero-filled once (include/ydbl.h)
-    nd = NmsDesc(cand_box.data_ptr(), cand_score.data_ptr(), cand_cls.data_ptr(), cand_idx.data_ptr(),
-                 cand_count.data_ptr(), bs, cap, float(iou_thres), int(max_det), int(max_nms), int(bool(agnostic)),
-                 float(max_wh), 0.0, 0.0, out.data_ptr(), cnt.data_ptr(), ws.data_ptr())
+    ws = nms_workspace(bs, cands.cap, max_nms, dev)
+    nd = NmsDesc(n=bs, iou_thres=float(iou_thres), max_det=int(max_det), max_nms=int(max_nms),
+                 agnostic=int(bool(agnostic)), max_wh=float(max_wh), out=out.data_ptr(), out_count=cnt.data_ptr(),
+                 workspace=ws.data_ptr(), **cands.fields())
     _lib.check(_lib.lib.ydbl_nms(nd, stream), "ydbl_nms")
     counts = cnt.tolist()
     return [out[i, : counts[i]] for i in range(bs)]
