@@ -73,6 +73,8 @@
  *                             (the index map's indicator, F.interpolate bilinear, > 0.5), as bit planes
  *   ydbl_mask_iou          <- mask_iou utils/metrics.py:137-153 as segment/val.py:213 calls it, popcount on bit planes
  *   ydbl_match_iou         <- segment/val.py:217: match_predictions on the mask IoU matrix
+ *   ydbl_pose_keypoints    <- Pose.kpts_decode nn/modules/head.py:396-401 for the rows the NMS kept, in fp32
+ *   ydbl_kpt_oks           <- kpt_iou utils/metrics.py:156-175 with the label areas of models/yolo/pose/val.py:192
  *   ydbl_confusion_matrix  <- ConfusionMatrix.process_batch utils/metrics.py:326-382 and its call sites in
  *                             DetectionValidator.update_metrics models/yolo/detect/val.py:140-159
  *   ydbl_coco_match        <- COCOeval.evaluateImg (the COCO detection protocol's per-image, per-category greedy
@@ -1074,6 +1076,56 @@ typedef struct {
   void* workspace; /* ydbl_match_workspace(n, max_det, n_gt, n_iou) bytes */
 } ydbl_match_iou_desc;
 int ydbl_match_iou(const ydbl_match_iou_desc* d, void* stream);
+
+/* Keypoints of the kept detections of a pose model (Pose.kpts_decode, nn/modules/head.py:396-401), one launch for a
+ * batch, behind ydbl_nms in the same graph.  For image b and slot k < min(count[b], max_det), keep_idx int32
+ * [n][max_det] (ydbl_nms's out_idx) names the anchor -- keep_idx itself when nc == 0, keep_idx / nc for the
+ * multi-label index anchor * nc + cls, ydbl_process_mask's rule -- and the anchor's K * ndim raw values are read from
+ * the level maps kpt[0..nl) ([n,h_l,w_l,K*ndim] views, f16 or f32, any channel stride >= K * ndim, anchors counted
+ * level after level, row-major).  With (gx, gy) the anchor's grid cell and s = stride[l] of its level, in fp32 from the
+ * stored value, every operation rounded on its own:
+ *   x = (v_x * 2 + gx) * s,   y = (v_y * 2 + gy) * s,   visibility = 1 / (1 + expf(-v))   (ndim == 3 only).
+ * v * 2 and * s are exact for the power-of-two strides, so x / y equal torch's fp32 evaluation of the reference formula
+ * on the same stored values bit for bit.  (Under half=True the reference decodes in fp16; this does not.)
+ * out fp32 [n][max_det][K][ndim], letterboxed-input pixels.  Slots at or past the count are written 0; an index outside
+ * the levels (or negative) gives a zero row.  No atomics, every output element written exactly once: identical from
+ * run to run.  1 <= max_det <= 4096, ndim 2 or 3.  One launch on `stream`, no allocation, no sync. */
+typedef struct {
+  ydbl_view kpt[3];
+  int32_t nl, nc;
+  float stride[3];
+  const int32_t* keep_idx;
+  const int32_t* count;
+  int32_t n, max_det;
+  int32_t K, ndim;
+  float* out;
+} ydbl_pose_kpt_desc;
+int ydbl_pose_keypoints(const ydbl_pose_kpt_desc* d, void* stream);
+
+/* Object keypoint similarity of every label against every detection slot of its own image: kpt_iou
+ * (utils/metrics.py:156-175) as PoseValidator._process_batch calls it (models/yolo/pose/val.py:190-193).  Labels are
+ * grouped by image as in ydbl_match_desc (gt_ofs int32 [n+1]); label g = gt_ofs[b] + l is image b's l-th label.
+ * pred_kpts fp32 [n][max_det][K][ndim] (ydbl_pose_keypoints' layout; only x, y are read), gt_kpts fp32 [n_gt][K][3]
+ * (x, y, visibility), gt_box fp32 [n_gt][4] xyxy, sigma fp32 [K].  In fp32, no contraction:
+ *   area = ((x2 - x1) * (y2 - y1)) * 0.53f,
+ *   e_k  = ((gx - px)^2 + (gy - py)^2) / ((((2 sigma_k)^2) * (area + 1e-7f)) * 2),
+ *   oks  = (sum of expf(-e_k) over the label's points with visibility != 0, in keypoint order) / (n_visible + 1e-7f).
+ * A label with no visible point gives 0.  oks fp32 [n_gt][max_det], ydbl_mask_iou's layout: row g against the slots
+ * of its own image, columns at or past the count written 0 -- what ydbl_match_iou reads.  K <= 64.  No atomics,
+ * every output element written exactly once.  One launch on `stream`, no allocation, no sync. */
+typedef struct {
+  const float* pred_kpts;
+  const int32_t* count;
+  int32_t n, max_det;
+  int32_t K, ndim;
+  const float* gt_kpts;
+  const float* gt_box;
+  const int32_t* gt_ofs;
+  int32_t n_gt;
+  const float* sigma;
+  float* oks;
+} ydbl_kpt_oks_desc;
+int ydbl_kpt_oks(const ydbl_kpt_oks_desc* d, void* stream);
 
 const char* ydbl_last_error(void);
 const char* ydbl_version(void);

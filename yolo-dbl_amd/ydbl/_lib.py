@@ -280,6 +280,20 @@ class MatchIouDesc(C.Structure):
                 ("workspace", C.c_void_p)]
 
 
+class PoseKptDesc(C.Structure):
+    """ydbl_pose_kpt_desc: the kept detections' keypoints, decoded in fp32 from the level maps keep_idx names."""
+    _fields_ = [("kpt", View * 3), ("nl", C.c_int32), ("nc", C.c_int32), ("stride", C.c_float * 3),
+                ("keep_idx", C.c_void_p), ("count", C.c_void_p), ("n", C.c_int32), ("max_det", C.c_int32),
+                ("K", C.c_int32), ("ndim", C.c_int32), ("out", C.c_void_p)]
+
+
+class KptOksDesc(C.Structure):
+    """ydbl_kpt_oks_desc: OKS of every label against the detection slots of its image -> [n_gt][max_det]."""
+    _fields_ = [("pred_kpts", C.c_void_p), ("count", C.c_void_p), ("n", C.c_int32), ("max_det", C.c_int32),
+                ("K", C.c_int32), ("ndim", C.c_int32), ("gt_kpts", C.c_void_p), ("gt_box", C.c_void_p),
+                ("gt_ofs", C.c_void_p), ("n_gt", C.c_int32), ("sigma", C.c_void_p), ("oks", C.c_void_p)]
+
+
 # name -> (argtypes, restype); every entry must exist in include/ydbl.h
 _P = C.c_void_p
 _VP = C.POINTER(View)
@@ -356,6 +370,8 @@ SIGNATURES = {
     "ydbl_gt_mask_bits": ([C.POINTER(GtBitsDesc), _P], C.c_int),
     "ydbl_mask_iou": ([C.POINTER(MaskIouDesc), _P], C.c_int),
     "ydbl_match_iou": ([C.POINTER(MatchIouDesc), _P], C.c_int),
+    "ydbl_pose_keypoints": ([C.POINTER(PoseKptDesc), _P], C.c_int),
+    "ydbl_kpt_oks": ([C.POINTER(KptOksDesc), _P], C.c_int),
     "ydbl_last_error": ([], C.c_char_p),
     "ydbl_version": ([], C.c_char_p),
 }

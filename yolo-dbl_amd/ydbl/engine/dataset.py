@@ -159,6 +159,24 @@ def verify_image_segments(im_file: str, lb_file: str, num_cls: int):
     return _verify_pair(im_file, lb_file, num_cls)
 
 
+def verify_image_keypoints(im_file: str, lb_file: str, num_cls: int, kpt_shape):
+    """verify_image_label with keypoint=True (U/data/utils.py:128-130, :155-159): every row has 5 + K * ndim columns,
+    the keypoints' xy at most 1 -> (hw, lb [n, 5], keypoints float32 [n, K, 3], msg).  Two-column keypoints get the
+    visibility column: 0 where x or y is negative, else 1."""
+    return _verify_pair(im_file, lb_file, num_cls, kpt_shape)
+
+
+def split_has_keypoints(img_path, kpt_shape) -> bool:
+    """Whether at least one label file of the split holds a pose row (5 + K * ndim columns)."""
+    want = 5 + int(kpt_shape[0]) * int(kpt_shape[1])
+    for lb_file in img2label_paths(get_img_files(img_path)):
+        if os.path.isfile(lb_file):
+            with open(lb_file) as f:
+                if any(len(x.split()) == want for x in f.read().strip().splitlines()):
+                    return True
+    return False
+
+
 def split_has_segments(img_path) -> bool:
     """Whether at least one label file of the split holds a polygon row (more than 6 columns)."""
     for lb_file in img2label_paths(get_img_files(img_path)):
@@ -169,8 +187,11 @@ def split_has_segments(img_path) -> bool:
     return False
 
 
-def _verify_pair(im_file: str, lb_file: str, num_cls: int):
+def _verify_pair(im_file: str, lb_file: str, num_cls: int, kpt_shape=None):
+    """The pair's (hw, lb [n, 5], extra, msg): extra = the rows' polygons, or with kpt_shape their keypoints."""
     from PIL import Image
+
+    ncol = 5 + int(kpt_shape[0]) * int(kpt_shape[1]) if kpt_shape is not None else 5
 
     try:
         with Image.open(im_file) as im:
@@ -182,20 +203,26 @@ def _verify_pair(im_file: str, lb_file: str, num_cls: int):
         if fmt not in IMG_FORMATS:
             raise ValueError(f"invalid image format {fmt}")
         msg = ""
-        lb = np.zeros((0, 5), dtype=np.float32)
+        lb = np.zeros((0, ncol), dtype=np.float32)
         segs = []
         if os.path.isfile(lb_file):
             with open(lb_file) as f:
                 rows = [x.split() for x in f.read().strip().splitlines() if len(x)]
-            if any(len(x) > 6 for x in rows):  # segments
+            if any(len(x) > 6 for x in rows) and kpt_shape is None:  # segments
                 classes = np.array([x[0] for x in rows], dtype=np.float32)
                 segs = [np.array(x[1:], dtype=np.float32).reshape(-1, 2) for x in rows]
                 rows = np.concatenate((classes.reshape(-1, 1), _segments2boxes(segs)), 1)
-            lb = np.array(rows, dtype=np.float32).reshape(-1, 5) if len(rows) else lb
+            if kpt_shape is not None:
+                if any(len(x) != ncol for x in rows):
+                    raise ValueError(f"labels require {ncol} columns each")
+                lb = np.array(rows, dtype=np.float32).reshape(-1, ncol) if len(rows) else lb
+            else:
+                lb = np.array(rows, dtype=np.float32).reshape(-1, 5) if len(rows) else lb
             if nl := len(lb):
-                if lb.shape[1] != 5:
+                if lb.shape[1] != ncol:
                     raise ValueError(f"labels require 5 columns, {lb.shape[1]} columns detected")
-                if lb[:, 1:].max() > 1:
+                points = lb[:, 5:].reshape(-1, int(kpt_shape[1]))[:, :2] if kpt_shape is not None else lb[:, 1:]
+                if points.max() > 1:
                     raise ValueError("non-normalized or out of bounds coordinates")
                 if lb.min() < 0:
                     raise ValueError("negative label values")
@@ -207,6 +234,13 @@ def _verify_pair(im_file: str, lb_file: str, num_cls: int):
                     if segs:
                         segs = [segs[x] for x in i]
                     msg = f"{im_file}: {nl - len(i)} duplicate labels removed"
+        if kpt_shape is not None:  # U/data/utils.py:155-160
+            K, ndim = int(kpt_shape[0]), int(kpt_shape[1])
+            kpts = lb.reshape(-1, ncol)[:, 5:].reshape(-1, K, ndim)
+            if ndim == 2:
+                vis = np.where((kpts[..., 0] < 0) | (kpts[..., 1] < 0), 0.0, 1.0).astype(np.float32)
+                kpts = np.concatenate([kpts, vis[..., None]], axis=-1)
+            return shape, np.ascontiguousarray(lb.reshape(-1, ncol)[:, :5]), np.ascontiguousarray(kpts), msg
         if len(segs) != len(lb):  # no polygon row in the file
             segs = [np.zeros((0, 2), dtype=np.float32) for _ in range(len(lb))]
         return shape, lb, segs, msg
@@ -301,11 +335,18 @@ class YOLOValDataset:
     ("segments"), an item's polygons go through the same resize + letterbox offsets as its boxes and become the
     overlap index map at a quarter of the letterboxed size (polygons2masks_overlap), ``cls`` / ``bboxes`` are
     reordered to the map's order (Format._format_segments, U/data/augment.py:2078-2094) and the batches carry
-    "masks".  With masks=False nothing of this exists."""
+    "masks".  With masks=False nothing of this exists.
+
+    keypoints=True with kpt_shape=(K, ndim) (pose validation, use_keypoints): the label rows have 5 + K * ndim columns
+    (verify_image_keypoints), an item's keypoints go through the same resize + letterbox offsets as its boxes and are
+    normalized by the letterboxed size like them, and the batches carry "keypoints" float32 [N, K, 3]."""
 
     def __init__(self, img_path, imgsz=640, batch_size=16, stride=32, rect=True, pad=0.5, single_cls=False,
-                 classes=None, num_cls=80, workers=8, masks=False):
+                 classes=None, num_cls=80, workers=8, masks=False, keypoints=False, kpt_shape=None):
         self.masks = bool(masks)
+        self.keypoints = bool(keypoints)
+        if self.keypoints and (self.masks or kpt_shape is None):
+            raise ValueError("keypoints=True needs kpt_shape=(K, ndim) and excludes masks=True")
         self.imgsz, self.batch_size, self.stride = int(imgsz), int(batch_size), int(stride)
         self.rect, self.pad, self.workers = bool(rect), float(pad), max(1, int(workers))
         im_files = get_img_files(img_path)
@@ -315,6 +356,8 @@ class YOLOValDataset:
         with ThreadPoolExecutor(self.workers) as ex:
             if self.masks:
                 res = list(ex.map(lambda a: verify_image_segments(*a, num_cls), zip(im_files, lb_files)))
+            elif self.keypoints:
+                res = list(ex.map(lambda a: verify_image_keypoints(*a, num_cls, kpt_shape), zip(im_files, lb_files)))
             else:
                 res = [(sh, lb, None, msg) for sh, lb, msg in
                        ex.map(lambda a: verify_image_label(*a, num_cls), zip(im_files, lb_files))]
@@ -325,6 +368,8 @@ class YOLOValDataset:
                 labels.append({"im_file": f, "shape": shape, "cls": lb[:, 0:1], "bboxes": lb[:, 1:]})
                 if self.masks:
                     labels[-1]["segments"] = segs
+                if self.keypoints:
+                    labels[-1]["keypoints"] = segs
         if not labels:
             raise FileNotFoundError(f"no valid images in {img_path}")
         if classes is not None:  # update_labels (U/data/base.py:132-149)
@@ -334,6 +379,8 @@ class YOLOValDataset:
                 lb["cls"], lb["bboxes"] = lb["cls"][j], lb["bboxes"][j]
                 if self.masks:
                     lb["segments"] = [sg for sg, k in zip(lb["segments"], j) if k]
+                if self.keypoints:
+                    lb["keypoints"] = lb["keypoints"][j]
         if single_cls:
             for lb in labels:
                 lb["cls"][:, 0] = 0
@@ -424,6 +471,14 @@ class YOLOValDataset:
                 polys.append(sg)
             item["masks"], order = polygons2masks_overlap((H, W), polys)
             item["cls"], item["bboxes"] = item["cls"][order], item["bboxes"][order]
+        if self.keypoints:  # Instances.denormalize / scale(1, 1) / add_padding, then Format's normalize, as the boxes
+            kp = lb["keypoints"].astype(np.float32).copy()
+            for k, (sc, off, full) in enumerate(((w, left, W), (h, top, H))):
+                kp[..., k] *= sc
+                kp[..., k] *= 1.0
+                kp[..., k] += off
+                kp[..., k] /= np.float32(full)
+            item["keypoints"] = kp
         return item
 
     def batches(self):
@@ -450,6 +505,8 @@ class YOLOValDataset:
                 if len(shapes) != 1:
                     raise RuntimeError(f"images of one batch letterbox to different shapes {sorted(shapes)}")
                 extra = {"masks": np.stack([it["masks"] for it in items])} if self.masks else {}
+                if self.keypoints:
+                    extra["keypoints"] = np.concatenate([it["keypoints"] for it in items])
                 yield {
                     **extra,
                     "frames": [it["img"] for it in items],

@@ -23,7 +23,8 @@ import torch
 
 from ..nn.tasks import DetectionModel, normalize_embed, weights_signature, ydbl_env
 from .results import Results
-from .session import (AugmentSession, DetectOptions, DetectSession, EmbedSession, check_segment, default_streams)
+from .session import (AugmentSession, DetectOptions, DetectSession, EmbedSession, check_pose, check_segment,
+                      default_streams)
 
 DEFAULTS = {"conf": 0.25, "iou": 0.7, "max_det": 300, "half": False, "fp8": False, "device": None, "agnostic_nms": False,
             "classes": None, "batch": 1, "verbose": False, "imgsz": 640,
@@ -213,7 +214,7 @@ class _LazyCounts:
 class Model:
     """U/engine/model.py:84-643 (detect task subset)."""
 
-    def __init__(self, model: str | Path = "yolov13n_DBL.yaml", task=None, verbose=False, nc=None):
+    def __init__(self, model: str | Path = "yolov13n_DBL.yaml", task=None, verbose=False, nc=None, kpt_shape=None):
         self.task = task or "detect"
         self.overrides = {}
         self.ckpt_path = None
@@ -229,7 +230,7 @@ class Model:
             ck = read_reference_checkpoint(model)
             if ck["yaml"] is None:
                 raise ValueError(f"{model} has no embedded model yaml: build from a config and call .load()")
-            self.model = DetectionModel(ck["yaml"], nc=nc, verbose=verbose)
+            self.model = DetectionModel(ck["yaml"], nc=nc, verbose=verbose, data_kpt_shape=kpt_shape)
             self._load_sd(ck["state_dict"])
             if ck["names"]:
                 self.model.names = ck["names"]
@@ -237,9 +238,11 @@ class Model:
         elif suffix == ".safetensors":
             raise ValueError("build from a config and call .load(weights): YOLO('yolov13n_DBL.yaml').load('w.safetensors')")
         else:
-            self.model = DetectionModel(model, nc=nc, verbose=verbose)
+            self.model = DetectionModel(model, nc=nc, verbose=verbose, data_kpt_shape=kpt_shape)
         if self.model.segment:  # U/nn/tasks.py guess_model_task: a Segment head is the "segment" task
             self.task = "segment"
+        if self.model.pose:  # and a Pose head the "pose" task
+            self.task = "pose"
         self.cfg = model
         self.overrides["model"] = model
 
@@ -312,6 +315,7 @@ class Model:
         load_labels)."""
         loss = check_loss(loss, augment, gather_rows)
         check_segment(self.model, fp8, loss, gather_rows)  # before any device work
+        check_pose(self.model, fp8, loss, gather_rows)
         if loss is not None:
             from ..nn.tasks import check_e2e_loss
 
@@ -326,7 +330,7 @@ class Model:
 
             warn_e2e_augment()
             augment = False
-        if augment and self.model.segment:  # the same rule: any class but DetectionModel
+        if augment and (self.model.segment or self.model.pose):  # the same rule: any class but DetectionModel
             from ..nn.tasks import warn_no_augment
 
             warn_no_augment()
@@ -455,7 +459,9 @@ class Model:
         # (_LazyCounts: one sync for the batch) -- on the copy path one device copy of det | count made now (the
         # session's buffers are reused by the next call); orig_img a view of the input batch (HWC, as LoadTensor
         # hands it over), made on first access.  speed["inference"] is the launch time.
-        mask_of = None
+        mask_of = kpt_of = None
+        if self.model.pose:  # the batch's keypoints (written inside the graph): one device copy, no host sync
+            kp = self._tensor_kpts(s, (h, w))
         if self.model.segment:  # one host sync for the counts, then the masks from the plan's buffers in place
             counts = cnt.tolist()
             mask_of = self._masks(s, det, counts, args, [(h, w)] * b)
@@ -475,10 +481,23 @@ class Model:
             box = lambda i: bo.detach().det[i, : counts[i]]  # noqa: E731
         else:
             box = lambda i: dets[i, : counts[i]]  # noqa: E731
+        if self.model.pose:  # PosePredictor.postprocess (U/models/yolo/pose/predict.py:50): the boxes are rounded
+            plain, box = box, (lambda i: _round_boxes(plain(i)))
+            kpt_of = lambda i: kp[i, : counts[i]]  # noqa: E731
         results = [Results(lambda i=i: hwc[i], path=f"image{i}.jpg", names=names, speed=speed, orig_shape=shape,
-                           boxes=lambda i=i: box(i), masks=(lambda i=i: mask_of(i)) if mask_of else None)
+                           boxes=lambda i=i: box(i), masks=(lambda i=i: mask_of(i)) if mask_of else None,
+                           keypoints=(lambda i=i: kpt_of(i)) if kpt_of else None)
                    for i in range(b)]
         return iter(results) if stream else results
+
+    @staticmethod
+    def _tensor_kpts(s, shape):
+        """A copy of the keypoints session `s` just wrote ([B, max_det, K, ndim], rows past the count zero), taken on
+        the current stream before `s` can run again, after scale_coords for a tensor source (gain 1, pad 0: the clip
+        to the input's extent alone, U/utils/ops.py:740-772)."""
+        from ..utils.ops import clip_coords
+
+        return clip_coords(s.kpts.clone(), shape)
 
     def _check_mask_args(self, args):
         """retina_masks / mask_dtype, on the host: mask_dtype must be torch.float32 (None) or torch.uint8; both mean
@@ -487,6 +506,7 @@ class Model:
 
         mask_dtype_code(args["mask_dtype"])
         check_segment(self.model, args["fp8"])  # a segmentation model has no fp8 path: before the device lookup
+        check_pose(self.model, args["fp8"])  # nor has a pose model
 
     @staticmethod
     def _masks(s, det, counts, args, shapes, boxes=None):
@@ -568,10 +588,17 @@ class Model:
             scaled.append(scale_boxes((h, w), det[i, : counts[i]].clone(), f.shape[:2]))
         mask_of = (self._masks(s, det, counts, args, [f.shape[:2] for f in frames], scaled)
                    if self.model.segment else None)
+        kpts = None
+        if self.model.pose:  # PosePredictor.postprocess (U/models/yolo/pose/predict.py:49-52)
+            from ..utils.ops import scale_coords
+
+            scaled = [_round_boxes(b_) for b_ in scaled]
+            kpts = [scale_coords((h, w), s.kpts[i, : counts[i]].clone(), f.shape[:2]) for i, f in enumerate(frames)]
         results = []
         for i, f in enumerate(frames):
             results.append(Results(f, path=paths[i] if paths else f"image{i}.jpg", names=self.model.names,
-                                   boxes=scaled[i], masks=mask_of(i) if mask_of else None))
+                                   boxes=scaled[i], masks=mask_of(i) if mask_of else None,
+                                   keypoints=kpts[i] if kpts is not None else None))
         t3 = time.perf_counter()
         speed = {"preprocess": (t1 - t0) * 1e3 / b, "inference": (t2 - t1) * 1e3 / b,
                  "postprocess": (t3 - t2) * 1e3 / b}
@@ -681,18 +708,24 @@ class Model:
         s, (det, cnt) = self._launch(s, (b, h, w), kw, lambda s, _: s(im, scale))
         # the tracker reads the session's det | count in place, on the stream that wrote them; then one copy of them
         # for the images that keep their predicted boxes (the session's buffers are reused by the next call)
-        seg = self.model.segment
-        out, oc, tr, *idx = ts.update(det, cnt, [(h, w)] * b, reset_each=not persist, want_idx=seg)
+        seg, pose = self.model.segment, self.model.pose
         dets, counts = det.clone(), cnt.clone()
+        if pose:  # the tracker sees the pose predictor's rounded boxes (U/models/yolo/pose/predict.py:50)
+            dets[..., :4] = dets[..., :4].round()
+            det = dets
+        out, oc, tr, *idx = ts.update(det, cnt, [(h, w)] * b, reset_each=not persist, want_idx=seg or pose)
         lazy = LazyTracks(ts, out, oc, tr, dets, counts)
         if seg:  # the predicted masks (one sync for the counts), re-ordered like the boxes (U/trackers/track.py:83-84)
             lazy.mask_src = (self._masks(s, det, cnt.tolist(), args, [(h, w)] * b), idx[0])
+        if pose:  # the keypoints follow their rows the same way; nothing synchronises
+            lazy.kpt_src = (self._tensor_kpts(s, (h, w)), idx[0])
         t2 = time.perf_counter()
         speed = {"preprocess": (t1 - t0) * 1e3 / b, "inference": (t2 - t1) * 1e3 / b, "postprocess": 0.0}
         hwc = _LazyHWC(im, scale)
         names = self.model.names
         return [Results(lambda i=i: hwc[i], path=f"image{i}.jpg", names=names, speed=speed, orig_shape=(h, w),
-                        boxes=lambda i=i: lazy[i], masks=(lambda i=i: lazy.masks(i)) if seg else None)
+                        boxes=lambda i=i: lazy[i], masks=(lambda i=i: lazy.masks(i)) if seg else None,
+                        keypoints=(lambda i=i: lazy.keypoints(i)) if pose else None)
                 for i in range(b)]
 
     def _track_frames(self, frames, args, dev, topt, paths=None):
@@ -717,16 +750,26 @@ class Model:
         shapes = [tuple(f.shape[:2]) for f in frames]
         for i, shp in enumerate(shapes):
             scale_boxes((h, w), dets[i], shp)
-        seg = self.model.segment
-        out, oc, tr, *idx = ts.update(dets, counts, shapes, reset_each=not persist, want_idx=seg)
+        seg, pose = self.model.segment, self.model.pose
+        if pose:  # the tracker sees the pose predictor's rounded boxes (U/models/yolo/pose/predict.py:50)
+            dets[..., :4] = dets[..., :4].round()
+        out, oc, tr, *idx = ts.update(dets, counts, shapes, reset_each=not persist, want_idx=seg or pose)
         lazy = LazyTracks(ts, out, oc, tr, dets, counts)
+        if pose:  # scale_coords of every slot to its frame (rows past the count are never handed out)
+            from ..utils.ops import scale_coords
+
+            kp = s.kpts.clone()
+            for i, shp in enumerate(shapes):
+                scale_coords((h, w), kp[i], shp)
+            lazy.kpt_src = (kp, idx[0])
         if seg:  # the predicted masks (one sync for the counts), re-ordered like the boxes (U/trackers/track.py:83-84)
             ch = counts.tolist()
             lazy.mask_src = (self._masks(s, det, ch, args, shapes, [dets[i, : ch[i]] for i in range(b)]), idx[0])
         t2 = time.perf_counter()
         speed = {"preprocess": (t1 - t0) * 1e3 / b, "inference": (t2 - t1) * 1e3 / b, "postprocess": 0.0}
         return [Results(f, path=paths[i] if paths else f"image{i}.jpg", names=self.model.names, speed=speed,
-                        boxes=lambda i=i: lazy[i], masks=(lambda i=i: lazy.masks(i)) if seg else None)
+                        boxes=lambda i=i: lazy[i], masks=(lambda i=i: lazy.masks(i)) if seg else None,
+                        keypoints=(lambda i=i: lazy.keypoints(i)) if pose else None)
                 for i, f in enumerate(frames)]
 
     def val(self, data=None, *, coco_eval=False, loss=False, **kwargs):
@@ -750,8 +793,13 @@ class Model:
         (ydbl.engine.validator.SegmentationValidator, U/models/yolo/segment/val.py): the result is SegmentMetrics
         (``box`` and ``seg``), ``validator.stats["tp_m"]`` the mask TP matrix.  overlap_mask=True (the default, as
         the reference's): ``"masks"`` is the uint8 index map [B, gh, gw]; False: planes [N, gh, gw] in label order.
-        Without masks such a model is scored on its boxes, with a warning."""
-        from .validator import DetectionValidator, SegmentationValidator
+        Without masks such a model is scored on its boxes, with a warning.
+        A pose model whose batches carry ground-truth ``"keypoints"`` ([N, K, 2 or 3], in label order and in the units
+        of the batch's ``bboxes``), or whose dataset's label rows have 5 + K * ndim columns, is scored on its keypoints
+        too (ydbl.engine.validator.PoseValidator, U/models/yolo/pose/val.py): the result is PoseMetrics (``box`` and
+        ``pose``), ``validator.stats["tp_p"]`` the keypoint TP matrix, and save_json rows gain "keypoints".  Without
+        keypoints such a model is scored on its boxes, with a warning.  loss=True raises for it (v8PoseLoss)."""
+        from .validator import DetectionValidator, PoseValidator, SegmentationValidator
 
         args = {**DEFAULTS, "conf": 0.001, "iou": 0.7, "batch": 16, "rect": True, "split": "val", "plots": True,
                 "save_json": False, "save_txt": False, "save_conf": False, "save_dir": None, **kwargs,
@@ -762,41 +810,58 @@ class Model:
             from ..nn.tasks import check_e2e_loss
 
             check_e2e_loss(self.model)  # an end2end model's criterion is E2EDetectLoss: before any device work
-        with_masks = False
+        check_pose(self.model, args["fp8"], args["loss"] or None, args.get("gather_rows"))
+        with_masks = with_kpts = False
         if self.model.segment:
             data, with_masks = _has_gt_masks(data, args["split"], len(self.model.names))
             if not with_masks:
                 _warn_seg_val()
             elif args.get("gather_rows") is not None:
                 raise ValueError("mask metrics are not implemented for the batch-sharded predictor (gather_rows)")
-        # kept: its per-image stats (tp, conf, pred_cls, target_cls; tp_m with mask metrics)
-        self.validator = (SegmentationValidator if with_masks else DetectionValidator)(self, args)
+        if self.model.pose:
+            data, with_kpts = _has_gt_masks(data, args["split"], len(self.model.names), key="keypoints",
+                                            kpt_shape=self.model.kpt_shape)
+            if not with_kpts:
+                _warn_pose_val()
+        # kept: its per-image stats (tp, conf, pred_cls, target_cls; tp_m with mask metrics, tp_p with keypoints)
+        cls = SegmentationValidator if with_masks else PoseValidator if with_kpts else DetectionValidator
+        self.validator = cls(self, args)
         return self.validator(data)
 
 
-def _has_gt_masks(data, split="val", n_names=0):
+def _round_boxes(boxes):
+    """A copy of the rows with the box columns rounded: scale_boxes(...).round() of PosePredictor.postprocess
+    (U/models/yolo/pose/predict.py:50)."""
+    boxes = boxes.clone()
+    boxes[:, :4] = boxes[:, :4].round()
+    return boxes
+
+
+def _has_gt_masks(data, split="val", n_names=0, key="masks", kpt_shape=None):
     """(data, whether val() computes mask metrics on it): an iterable of in-memory batches does when its first batch
     carries "masks" (the iterable is handed back with that batch in place); a dataset does when at least one label
-    file of the split holds a polygon row."""
+    file of the split holds a polygon row.  key="keypoints" with kpt_shape: the same question for a pose model's
+    keypoint metrics (a dataset does when a label row has 5 + K * ndim columns)."""
     import itertools
     import os
 
     if data is None:
         return data, False
     if isinstance(data, (str, os.PathLike, dict)):
-        from .dataset import split_has_segments
+        from .dataset import split_has_keypoints, split_has_segments
         from .validator import val_source
 
-        return data, split_has_segments(val_source(data, split, n_names)[0])
+        src = val_source(data, split, n_names)[0]
+        return data, split_has_keypoints(src, kpt_shape) if key == "keypoints" else split_has_segments(src)
     if isinstance(data, (list, tuple)):  # known up front: said before any device work
-        has = [isinstance(b, dict) and "masks" in b for b in data]
+        has = [isinstance(b, dict) and key in b for b in data]
         if any(has) and not all(has):
-            raise ValueError("val(): only some batches carry 'masks'; mask metrics need them in every batch")
+            raise ValueError(f"val(): only some batches carry '{key}'; {key[:-1]} metrics need them in every batch")
     it = iter(data)
     first = next(it, None)
     if first is None:
         return [], False
-    return itertools.chain([first], it), isinstance(first, dict) and "masks" in first
+    return itertools.chain([first], it), isinstance(first, dict) and key in first
 
 
 _SEG_VAL_WARNED = False
@@ -812,6 +877,20 @@ def _warn_seg_val():
         warnings.warn("val() on a segmentation model reports the box metrics only: mask metrics (mask mAP) are not "
                       "computed", stacklevel=3)
         _SEG_VAL_WARNED = True
+
+
+_POSE_VAL_WARNED = False
+
+
+def _warn_pose_val():
+    """val() on a pose model without ground-truth keypoints: the box report, as for Detect.  Said once."""
+    global _POSE_VAL_WARNED
+    if not _POSE_VAL_WARNED:
+        import warnings
+
+        warnings.warn("val() on a pose model without ground-truth keypoints reports the box metrics only: keypoint "
+                      "metrics (pose mAP) are not computed", stacklevel=3)
+        _POSE_VAL_WARNED = True
 
 
 class YOLO(Model):

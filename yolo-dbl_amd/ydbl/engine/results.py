@@ -1,4 +1,4 @@
-"""Results / Boxes / Masks containers: the `boxes` and `masks` subset of U/engine/results.py:187-1202.
+"""Results / Boxes / Masks / Keypoints containers: the `boxes`, `masks` and `keypoints` subset of U/engine/results.py:187-1202.
 
 ``Boxes.data`` is ``[n, 6] = x1, y1, x2, y2, conf, cls`` exactly as the
 reference builds it in DetectionPredictor.postprocess
@@ -167,14 +167,71 @@ class Masks:
         raise NotImplementedError(_NO_POLYGONS)
 
 
-class Results:
-    """U/engine/results.py:187- (boxes, masks, names, orig_shape, speed)."""
+class Keypoints:
+    """U/engine/results.py:1255-1375 — the keypoints of one image: ``data`` [k, K, ndim] (x, y[, visibility]) in the
+    original image's pixels, one row per box, in box order.  With a visibility column, points below 0.5 get
+    xy = 0 (in place, as the reference's constructor does it, :1305-1311)."""
 
-    def __init__(self, orig_img, path, names, boxes=None, speed=None, orig_shape=None, masks=None):
+    def __init__(self, keypoints, orig_shape):
+        if keypoints.ndim == 2:
+            keypoints = keypoints[None, :]
+        if keypoints.shape[2] == 3:  # x, y, visibility
+            mask = keypoints[..., 2] < 0.5
+            keypoints[..., :2][mask] = 0
+        self.data = keypoints
+        self.orig_shape = tuple(orig_shape)
+        self.has_visible = self.data.shape[-1] == 3
+
+    def _new(self, data):
+        return Keypoints(data, self.orig_shape)
+
+    def cpu(self):
+        return self._new(self.data.cpu()) if isinstance(self.data, torch.Tensor) else self
+
+    def numpy(self):
+        return self._new(self.data.cpu().numpy() if isinstance(self.data, torch.Tensor) else self.data)
+
+    def cuda(self):
+        return self._new(torch.as_tensor(self.data).cuda())
+
+    def to(self, *args, **kwargs):
+        return self._new(torch.as_tensor(self.data).to(*args, **kwargs))
+
+    def __len__(self):
+        return len(self.data)
+
+    def __getitem__(self, idx):
+        return self._new(self.data[idx])
+
+    @property
+    def shape(self):
+        return self.data.shape
+
+    @property
+    def xy(self):
+        return self.data[..., :2]
+
+    @property
+    def xyn(self):
+        xy = self.xy.clone() if isinstance(self.xy, torch.Tensor) else np.copy(self.xy)
+        xy[..., 0] /= self.orig_shape[1]
+        xy[..., 1] /= self.orig_shape[0]
+        return xy
+
+    @property
+    def conf(self):
+        return self.data[..., 2] if self.has_visible else None
+
+
+class Results:
+    """U/engine/results.py:187- (boxes, masks, keypoints, names, orig_shape, speed)."""
+
+    def __init__(self, orig_img, path, names, boxes=None, speed=None, orig_shape=None, masks=None, keypoints=None):
         """orig_img / boxes / masks may also be zero-argument callables producing them (predict() hands over per-image
         views of its batch buffers that way: built on first access, not for every image of every batch).  masks: a
         [k, H, W] tensor, or None -- as for an image without detections (U/models/yolo/segment/predict.py:86-87)."""
         self._masks_src, self._masks = masks, None
+        self._kpts_src, self._kpts = keypoints, None  # [k, K, ndim] (or a callable), None for a model without them
         self._orig_img = orig_img
         if orig_shape is None and orig_img is not None:
             orig_shape = (orig_img() if callable(orig_img) else orig_img).shape[:2]
@@ -216,6 +273,17 @@ class Results:
     def masks(self, v):
         self._masks, self._masks_src = v, None
 
+    @property
+    def keypoints(self):
+        if self._kpts is None and self._kpts_src is not None:
+            src = self._kpts_src() if callable(self._kpts_src) else self._kpts_src
+            self._kpts, self._kpts_src = (Keypoints(src, self.orig_shape) if src is not None else None), None
+        return self._kpts
+
+    @keypoints.setter
+    def keypoints(self, v):
+        self._kpts, self._kpts_src = v, None
+
     def __len__(self):
         return 0 if self.boxes is None else len(self.boxes)
 
@@ -228,6 +296,8 @@ class Results:
             r.boxes = getattr(self.boxes, fn)(*args, **kwargs)
         if self.masks is not None:
             r.masks = getattr(self.masks, fn)(*args, **kwargs)
+        if self.keypoints is not None:
+            r.keypoints = getattr(self.keypoints, fn)(*args, **kwargs)
         return r
 
     def new(self):
@@ -260,11 +330,18 @@ class Results:
         if self.boxes is not None and len(self.boxes):
             b = self.boxes.cpu() if isinstance(self.boxes.data, torch.Tensor) else self.boxes
             xywhn = torch.as_tensor(b.xywhn)
+            kpts = self.keypoints
             for j in range(len(b)):
                 d = b[j]
                 c, conf = int(torch.as_tensor(d.cls).item()), float(torch.as_tensor(d.conf).item())
                 tid = None if d.id is None else int(torch.as_tensor(d.id).item())
-                line = (c, *xywhn[j].view(-1).tolist()) + (conf,) * save_conf + (() if tid is None else (tid,))
+                line = (c, *xywhn[j].view(-1).tolist())
+                if kpts is not None:  # U/engine/results.py:709-711: xyn (and the visibility) behind the box
+                    kj = kpts[j]
+                    xyn = torch.as_tensor(kj.xyn).cpu()
+                    kp = torch.cat((xyn, torch.as_tensor(kj.conf).cpu()[..., None]), 2) if kj.has_visible else xyn
+                    line += (*kp.reshape(-1).tolist(),)
+                line += (conf,) * save_conf + (() if tid is None else (tid,))
                 texts.append(("%g " * len(line)).rstrip() % line)
         if texts:
             Path(txt_file).parent.mkdir(parents=True, exist_ok=True)
@@ -283,13 +360,16 @@ class Results:
     def to_json(self, normalize=False, decimals=5):
         return json.dumps(self.summary(normalize=normalize, decimals=decimals), indent=2)
 
-    def plot(self, conf=True, line_width=None, labels=True, boxes=True, img=None, masks=True):
-        """Annotated copy of the original image (HWC uint8 BGR ndarray, like the reference's plot()).  Mask drawing is
-        not implemented: a result with masks raises NotImplementedError unless masks=False (boxes only)."""
+    def plot(self, conf=True, line_width=None, labels=True, boxes=True, img=None, masks=True, keypoints=True):
+        """Annotated copy of the original image (HWC uint8 BGR ndarray, like the reference's plot()).  Mask and
+        keypoint drawing is not implemented: a result with masks (keypoints) raises NotImplementedError unless
+        masks=False (keypoints=False), which draws the boxes alone."""
         from PIL import Image, ImageDraw
 
         if masks and self.masks is not None:
             raise NotImplementedError("plot() does not draw masks; plot(masks=False) draws the boxes alone")
+        if keypoints and self.keypoints is not None:
+            raise NotImplementedError("plot() does not draw keypoints; plot(keypoints=False) draws the boxes alone")
 
         im = self.orig_img if img is None else img
         if isinstance(im, torch.Tensor):  # CHW/HWC float 0..1 tensor source -> HWC uint8 BGR
@@ -333,7 +413,8 @@ class Results:
         if self.boxes is None:
             return out
         h, w = self.orig_shape
-        for row in self.boxes.data.tolist():
+        kh, kw = (h, w) if normalize else (1, 1)
+        for i, row in enumerate(self.boxes.data.tolist()):
             (x1, y1, x2, y2), conf, cls = row[:4], row[-2], row[-1]  # xyxy, track id when tracking, conf, cls
             if normalize:
                 x1, x2, y1, y2 = x1 / w, x2 / w, y1 / h, y2 / h
@@ -341,6 +422,12 @@ class Results:
                         "box": {k: round(v, decimals) for k, v in zip(("x1", "y1", "x2", "y2"), (x1, y1, x2, y2))}})
             if self.boxes.is_track:  # U/engine/results.py:803-804
                 out[-1]["track_id"] = int(row[-3])
+            if self.keypoints is not None:  # U/engine/results.py:810-816
+                k = torch.as_tensor(self.keypoints.data[i]).cpu()
+                out[-1]["keypoints"] = {"x": (k[:, 0] / kw).numpy().round(decimals).tolist(),
+                                        "y": (k[:, 1] / kh).numpy().round(decimals).tolist()}
+                if self.keypoints.has_visible:
+                    out[-1]["keypoints"]["visible"] = k[:, 2].numpy().round(decimals).tolist()
         return out
 
     def verbose(self):

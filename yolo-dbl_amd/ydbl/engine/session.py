@@ -132,6 +132,28 @@ def check_segment(model, fp8=False, loss=None, gather_rows=None):
                                   "(gather_rows): its record rows carry boxes only")
 
 
+def is_pose(model) -> bool:
+    """The model's head is a Pose (U/nn/modules/head.py:328-401): its sessions also produce keypoints."""
+    from ..nn.modules import Pose
+
+    return isinstance(model.model[-1], Pose)
+
+
+def check_pose(model, fp8=False, loss=None, gather_rows=None):
+    """A pose model's scope guards, on the host before any device work: no fp8 (no calibration record covers the
+    keypoint branch), no loss (the criterion is v8PoseLoss, U/utils/loss.py) and no batch-sharded predictor (its
+    record rows carry boxes only)."""
+    if not is_pose(model):
+        return
+    if fp8:
+        raise NotImplementedError("fp8=True on a pose model: no calibration record exists for the keypoint branch")
+    if loss is not None and loss is not False:
+        raise NotImplementedError("the loss of a pose model is v8PoseLoss, which is not implemented")
+    if gather_rows is not None:
+        raise NotImplementedError("pose models are not implemented for the batch-sharded predictor "
+                                  "(gather_rows): its record rows carry boxes only")
+
+
 def _f32(v: float) -> float:
     """v rounded to fp32, as torch does when it multiplies a Python float into an fp32 tensor."""
     return torch.tensor(v, dtype=torch.float32).item()
@@ -275,6 +297,7 @@ class DetectSession(BatchSession):
 
             check_e2e_loss(model)
         check_segment(model, opt.fp8, opt.loss, gather_rows)  # a Segment head: no fp8, loss or record rows
+        check_pose(model, opt.fp8, opt.loss, gather_rows)  # a Pose head: the same three
         if opt.fp8:
             for name in ("C2PSA", "SPPF"):
                 if any(type(m).__name__ == name for m in model.modules()):
@@ -312,7 +335,8 @@ class DetectSession(BatchSession):
             _outputs = (det_v, cnt_v, torch.empty((batch, 4 + self.nc, A), dtype=torch.float32, device=device)
                         if opt.keep_pred else None)
         if _outputs is not None:  # record rows, or slices of a split session's shared outputs
-            self.det, self.count, self.pred = _outputs
+            self.det, self.count, self.pred, *kp = _outputs
+            self.kpts = kp[0] if kp else None
         elif len(self.bounds) > 1:
             self._alloc_outputs(A)
         self._bind = _bind
@@ -336,14 +360,20 @@ class DetectSession(BatchSession):
         self.nc = model.model[-1].nc
         self.det = self.count = self.pred = None
         self.segment = is_segment(model)  # a Segment head: the NMS also writes keep_idx, masks() reads plan.seg
+        self.pose = is_pose(model)  # a Pose head: keep_idx too, and ydbl_pose_keypoints behind the NMS writes kpts
+        self.kpts = None
 
     def _alloc_outputs(self, A: int):
         self.det, self.count, self.out_flat = _det_count(self.batch, self.max_det, self.device)
         self.pred = (torch.empty((self.batch, 4 + self.nc, A), dtype=torch.float32, device=self.device)
                      if self.opt.keep_pred else None)
+        if self.pose and self.opt.nms:  # [B, max_det, K, ndim]: one buffer, each sub-batch plan writes its rows
+            K, ndim = self.model.model[-1].kpt_shape
+            self.kpts = torch.zeros((self.batch, self.max_det, K, ndim), dtype=torch.float32, device=self.device)
 
     def _child(self, i: int, a: int, b: int):
-        outs = (self.det[a:b], self.count[a:b], self.pred[a:b] if self.pred is not None else None)
+        outs = (self.det[a:b], self.count[a:b], self.pred[a:b] if self.pred is not None else None,
+                self.kpts[a:b] if self.kpts is not None else None)
         return DetectSession(self.model, b - a, self.h, self.w, device=self.device, options=self.opt, _outputs=outs,
                              _bind=(self.bind_ptrs[0, i:i + 1], self.bind_amax[0]))
 
@@ -361,9 +391,12 @@ class DetectSession(BatchSession):
             tail.emit_decode(cm.levels)
             tail.emit_topk(self.h, self.w)
             return plan
-        tail = self.tail = NmsTail(plan, self.batch, self.A, head, opt, *outs, segment=self.segment)
+        tail = self.tail = NmsTail(plan, self.batch, self.A, head, opt, *outs, segment=self.segment, pose=self.pose,
+                                   kpts=self.kpts)
         dd = tail.emit_decode(cm.levels)
         tail.emit_nms(self.h, self.w)
+        if self.pose:  # the kept rows' keypoints, inside the graph
+            tail.emit_keypoints(plan.pose)
         if opt.loss is not None:
             self._emit_loss(plan, cm, dd, opt.loss)
         return plan
@@ -479,6 +512,16 @@ class DetectSession(BatchSession):
                             keep_idx=part.keep_idx[i - a], mc=mcv, nc=self.nc if part.multi_label else 0, slots=k)
         return out
 
+    # ------------------------------------------------------------------ keypoints (a Pose head)
+    def pose_outputs(self):
+        """kpt [B, nk, A] of the last launch as a fresh tensor of the session's dtype: the raw keypoint maps, the
+        reference's Pose.forward output (U/nn/modules/head.py:367)."""
+        from ..nn.modules import pose_raw
+
+        if not self.pose:
+            raise RuntimeError("pose_outputs(): the model's head is not a Pose")
+        return torch.cat([pose_raw(p.compiled.plan.pose) for p in self.parts])
+
     # What the tail owns, under the names it has on a session; a split session has them on its children only, except:
     cand_box, cand_score, cand_cls, cand_idx = (_of_tail("cands." + n) for n in ("box", "score", "cls", "idx"))
     cap, multi_label, keep_idx, tile_masks = (_of_tail(n) for n in ("cap", "multi_label", "keep_idx", "tile_masks"))
@@ -512,6 +555,11 @@ class DetectSession(BatchSession):
         nds = [st.args[0] for p in parts for st in p.plan.steps if st.fn.__name__ in ("ydbl_nms", "ydbl_detect_topk")]
         for nd, (a, b) in zip(nds, self.bounds):
             nd.out, nd.out_count = det[a:b].data_ptr(), count[a:b].data_ptr()
+        # a Pose head: the keypoint launch reads the slot's counts; kpts stays the session's own buffer (the caller
+        # copies it behind the replay: Model.predict)
+        kds = [st.args[0] for p in parts for st in p.plan.steps if st.fn.__name__ == "ydbl_pose_keypoints"]
+        for kd, (a, b) in zip(kds, self.bounds):
+            kd.count = count[a:b].data_ptr()
 
     def launch_bound(self, x: torch.Tensor) -> "BoundOutputs":
         """predict()'s path for a device batch: the plans read x in place (include/ydbl.h ydbl_input_bind) -- no

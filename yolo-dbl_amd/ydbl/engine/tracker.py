@@ -188,6 +188,14 @@ class LazyTracks:
         return self.out[i, : oc[i]] if tr[i] else self.dets[i, : cnt[i]]
 
     mask_src = None  # a segmentation model's track(): (i -> the image's predicted masks or None, out_idx)
+    kpt_src = None  # a pose model's track(): (the batch's keypoints [n, max_det, K, ndim], out_idx)
+
+    def keypoints(self, i):
+        """Image i's keypoints in the order of its boxes: the predicted rows picked by the track rows' detection
+        indices when the image got tracks (results[i][idx], U/trackers/track.py:83-84), else as predicted."""
+        oc, tr, cnt = self._sync()
+        kp, idx = self.kpt_src
+        return kp[i][idx[i, : oc[i]].long()] if tr[i] else kp[i, : cnt[i]]
 
     def masks(self, i):
         """Image i's masks in the order of its boxes: the predicted masks picked by the track rows' detection indices

@@ -39,6 +39,10 @@ copied or synchronised for it.
 A segmentation model whose batches carry ground-truth ``"masks"`` (or whose dataset has polygon labels) is scored by
 SegmentationValidator below: the same run plus the mask TP matrix ``stats["tp_m"]``, matched on the device on bit
 planes, and SegmentMetrics.
+
+A pose model whose batches carry ground-truth ``"keypoints"`` (or whose dataset has pose label rows) is scored by
+PoseValidator: the same run plus the keypoint TP matrix ``stats["tp_p"]`` -- OKS on the device (ydbl_kpt_oks), then
+ydbl_match_iou -- and PoseMetrics.
 """
 
 from __future__ import annotations
@@ -53,8 +57,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..utils.metrics import (COCO_AREA_RNG, COCO_IOU_THRS, COCO_MAX_DETS, IOUV, LOGGER, ConfusionMatrix, DetMetrics,
-                             SegmentMetrics, coco_summary_lines)
+from ..utils.metrics import (COCO_AREA_RNG, COCO_IOU_THRS, COCO_MAX_DETS, IOUV, LOGGER, OKS_SIGMA, ConfusionMatrix,
+                             DetMetrics, PoseMetrics, SegmentMetrics, coco_summary_lines)
 from .model import load_tensor_source, select_device
 
 
@@ -226,6 +230,7 @@ def val_source(data, split: str, n_names: int):
 class DetectionValidator:
     stat_keys = ("tp", "conf", "pred_cls", "target_cls")
     with_masks = False
+    tp2_key = "tp_m"  # the second TP matrix of a subclass (_match_masks): "tp_m" for masks, "tp_p" for keypoints
 
     def __init__(self, model, args):
         self.model = model
@@ -253,7 +258,7 @@ class DetectionValidator:
         else:
             for batch in data:
                 self._run_tensor_batch(batch, dev)
-        st = {k: torch.cat(v, 0).numpy() if v else np.zeros((0, 10) if k in ("tp", "tp_m") else 0)
+        st = {k: torch.cat(v, 0).numpy() if v else np.zeros((0, 10) if k in ("tp", "tp_m", "tp_p") else 0)
               for k, v in self.stats.items()}
         # get_stats (val.py:179-187)
         self.nt_per_class = np.bincount(st["target_cls"].astype(int), minlength=self.nc)
@@ -363,9 +368,23 @@ class DetectionValidator:
                                      if a.get("loss") else {}))
 
     def _match_masks(self, det_d, cnt_d, grouped, bidx, single):
-        """The mask TP matrix of the batch on the device, launched behind the box matching; None here: the
-        SegmentationValidator's step."""
+        """The second TP matrix of the batch (masks, keypoints) on the device, launched behind the box matching; None
+        here: a subclass's step."""
         return None
+
+    def _dataset_kw(self) -> dict:
+        """What the subclass asks of YOLOValDataset beside the boxes."""
+        return {"masks": True} if self.with_masks else {}
+
+    def _native_extra(self, hb, gain, pad, ori):
+        """A dataset batch's further predictions and labels brought to native space (device gain [B], pad [B, 2],
+        ori (w, h) [B, 2]); nothing here."""
+
+    def _json_rows(self, pred, si, im_file) -> list:
+        return pred_to_json(pred, im_file)
+
+    def _save_txt(self, pred, si, shape, file):
+        save_one_txt(pred, bool(self.args.get("save_conf", False)), shape, self.model.names, file)
 
     def _run_tensor_batch(self, batch, dev):
         if not self.with_masks and "masks" in batch and getattr(self.model.model, "segment", False):
@@ -392,7 +411,7 @@ class DetectionValidator:
         imgsz = max(math.ceil(imgsz / stride) * stride, stride)  # check_imgsz (U/utils/checks.py)
         ds = YOLOValDataset(src, imgsz=imgsz, batch_size=a.get("batch", 16), stride=stride, rect=a.get("rect", True),
                             single_cls=a.get("single_cls", False), classes=a.get("classes"), num_cls=num_cls,
-                            workers=a.get("workers", 8), **({"masks": True} if self.with_masks else {}))
+                            workers=a.get("workers", 8), **self._dataset_kw())
         self.dataset = ds
         for hb in ds.batches():
             H, W = hb["shape"]
@@ -412,6 +431,7 @@ class DetectionValidator:
             _scale_clip(det_n[..., :4], pad[:, None, :], gain[:, None, None], ori[:, None, :])
             bidx = torch.from_numpy(hb["batch_idx"]).long()
             native = native_labels(hb)
+            self._native_extra(hb, gain, pad, ori)
             self._update(det_n, cnt_d, native, torch.from_numpy(hb["cls"]).float(), bidx,
                          im_files=hb["im_file"], ori_shapes=hb["ori_shape"])
 
@@ -448,7 +468,7 @@ class DetectionValidator:
                 if nl:
                     self.stats["tp"].append(torch.zeros(0, len(self.iouv), dtype=torch.bool))
                     if tp_m_all is not None:  # segment/val.py:115-118: the (0, n_iou) block
-                        self.stats["tp_m"].append(torch.zeros(0, len(self.iouv), dtype=torch.bool))
+                        self.stats[self.tp2_key].append(torch.zeros(0, len(self.iouv), dtype=torch.bool))
                     self.stats["conf"].append(torch.zeros(0))
                     self.stats["pred_cls"].append(torch.zeros(0))
                     self.stats["target_cls"].append(cls)
@@ -458,16 +478,15 @@ class DetectionValidator:
                 pred[:, 5] = 0
             self.stats["tp"].append(tp_all[si, :npr])
             if tp_m_all is not None:
-                self.stats["tp_m"].append(tp_m_all[si, :npr])
+                self.stats[self.tp2_key].append(tp_m_all[si, :npr])
             self.stats["conf"].append(pred[:, 4])
             self.stats["pred_cls"].append(pred[:, 5])
             self.stats["target_cls"].append(cls)
             self.target_img.append(cls.unique())
             if save and self.args.get("save_json"):
-                self.jdict.extend(pred_to_json(pred, im_files[si]))
+                self.jdict.extend(self._json_rows(pred, si, im_files[si]))
             if save and self.args.get("save_txt"):
-                save_one_txt(pred, bool(self.args.get("save_conf", False)), ori_shapes[si], self.model.names,
-                             self.save_dir / "labels" / f"{Path(im_files[si]).stem}.txt")
+                self._save_txt(pred, si, ori_shapes[si], self.save_dir / "labels" / f"{Path(im_files[si]).stem}.txt")
 
 
 class SegmentationValidator(DetectionValidator):
@@ -544,6 +563,127 @@ class SegmentationValidator(DetectionValidator):
         """segment/val.py:53-69 with this fork's mAP75 column in both groups."""
         return ("%22s" + "%11s" * 12) % ("Class", "Images", "Instances", "Box(P", "R", "mAP50", "mAP75", "mAP50-95)",
                                          "Mask(P", "R", "mAP50", "mAP75", "mAP50-95)")
+
+
+def gt_visibility(kpts: torch.Tensor) -> torch.Tensor:
+    """Ground-truth keypoints [N, K, 2 or 3] as [N, K, 3]: two-column points get the reference's visibility column
+    (U/data/utils.py:155-159: 0 where x or y is negative, else 1)."""
+    if kpts.dim() != 3 or kpts.shape[-1] not in (2, 3):
+        raise ValueError(f"'keypoints' must be [N, K, 2 or 3], got {tuple(kpts.shape)}")
+    if kpts.shape[-1] == 3:
+        return kpts
+    vis = torch.where((kpts[..., 0] < 0) | (kpts[..., 1] < 0), 0.0, 1.0).to(kpts.dtype)
+    return torch.cat([kpts, vis[..., None]], -1)
+
+
+class PoseValidator(DetectionValidator):
+    """PoseValidator (U/models/yolo/pose/val.py): the detection validator plus the keypoint TP matrix
+    ``stats["tp_p"]`` and PoseMetrics.  Reached by Model.val when the model has a Pose head and ground-truth
+    keypoints are supplied: tensor batches carry ``"keypoints"`` [N, K, 2 or 3] in label order, in the units of the
+    batch's ``bboxes`` (pixels of the input image); a dataset's label rows have 5 + K * ndim columns.
+
+    Per batch, right behind the box matching on the same stream and before the session runs again: the session's
+    keypoints (written inside the graph by ydbl_pose_keypoints) and the labels' are brought to the space the boxes
+    are matched in -- scale_coords: for tensor batches the clip to the input alone (gain 1, pad 0), for a dataset
+    scale_coords(ratio_pad) to the native image (val.py:86-104) --, then ydbl_kpt_oks (the label areas from the label
+    boxes, val.py:192) and ydbl_match_iou (val.py:197).  Nothing of it is read back but the [B, max_det, n_iou]
+    matrix, together with the box one (and the keypoints themselves for save_json / save_txt).  coco_eval, the
+    confusion matrix and loss stay box-based."""
+
+    stat_keys = ("tp", "tp_p", "conf", "pred_cls", "target_cls")
+    tp2_key = "tp_p"
+
+    def __init__(self, model, args):
+        super().__init__(model, args)
+        self.metrics = PoseMetrics(names=model.names)
+        self.kpt_shape = list(model.model.kpt_shape)
+        K = self.kpt_shape[0]
+        self.sigma = OKS_SIGMA if self.kpt_shape == [17, 3] else np.ones(K) / K  # val.py:77-84
+        self._kpts_host = None
+
+    def _launch(self, s, im, gt):
+        self._sess = s  # the keypoint step reads its kpts in place
+        return super()._launch(s, im, gt)
+
+    def _dataset_kw(self) -> dict:
+        return {"keypoints": True, "kpt_shape": self.kpt_shape}
+
+    def _check_gt(self, kp):
+        kp = gt_visibility(torch.as_tensor(kp).float())
+        if kp.shape[1] != self.kpt_shape[0]:
+            raise ValueError(f"'keypoints' holds {kp.shape[1]} points per label, the model {self.kpt_shape[0]}")
+        return kp
+
+    def _run_tensor_batch(self, batch, dev):
+        from ..utils.ops import clip_coords
+
+        if "keypoints" not in batch:
+            raise ValueError("val() with keypoint metrics: every batch must carry 'keypoints' (only some of them do)")
+        h, w = batch["img"].shape[-2:]
+        self._gt_kpts = clip_coords(self._check_gt(batch["keypoints"]).clone(), (h, w))  # scale_coords: gain 1, pad 0
+        self._pred_space = lambda kp: clip_coords(kp, (h, w))
+        super()._run_tensor_batch(batch, dev)
+
+    def _native_extra(self, hb, gain, pad, ori):
+        """_prepare_batch / _prepare_pred (val.py:86-104) of one dataset batch: the labels' keypoints per image on the
+        host in fp32 torch ops, as the reference runs them; the predictions' for the whole block on the device."""
+        from ..utils.ops import scale_coords
+
+        H, W = hb["shape"]
+        kp = self._check_gt(hb["keypoints"]).clone()
+        bidx = torch.from_numpy(hb["batch_idx"]).long()
+        for si in range(len(hb["ori_shape"])):
+            idx = bidx == si
+            if idx.any():
+                k = kp[idx]
+                k[..., 0] *= W
+                k[..., 1] *= H
+                kp[idx] = scale_coords((H, W), k, hb["ori_shape"][si], ratio_pad=hb["ratio_pad"][si])
+        self._gt_kpts = kp
+
+        def pred_space(p):  # scale_coords(ratio_pad) + clip_coords on the padded [B, max_det, K, ndim] block
+            p[..., 0:2] -= pad[:, None, None, :]
+            p[..., 0:2] /= gain[:, None, None, None]
+            p[..., 0:2] = torch.minimum(p[..., 0:2].clamp(min=0), ori[:, None, None, :])
+            return p
+
+        self._pred_space = pred_space
+
+    def _match_masks(self, det_d, cnt_d, grouped, bidx, single):
+        from ..utils.ops import kpt_oks
+
+        dev = det_d.device
+        boxes, cls, ofs, n_gt = grouped
+        order = torch.argsort(torch.as_tensor(bidx).reshape(-1).long(), stable=True)  # group_labels' order
+        if self._gt_kpts.shape[0] != n_gt:
+            raise ValueError(f"'keypoints' holds {self._gt_kpts.shape[0]} labels, 'bboxes' {n_gt}")
+        gt = self._gt_kpts[order].to(dev).contiguous()
+        pred = self._pred_space(self._sess.kpts.clone())
+        sigma = torch.as_tensor(np.asarray(self.sigma), dtype=torch.float32).to(dev)
+        oks = kpt_oks(pred, cnt_d.to(torch.int32).contiguous(), gt, boxes, ofs, sigma)
+        want = self.save_dir is not None and (self.args.get("save_json") or self.args.get("save_txt"))
+        self._kpts_host = pred.cpu() if want else None
+        return match_iou_batch(det_d, cnt_d, oks, cls, ofs, self.iouv, single)
+
+    def _json_rows(self, pred, si, im_file) -> list:
+        """pred_to_json (val.py:238-253): the rows gain "keypoints", the detection's K * ndim values."""
+        rows = pred_to_json(pred, im_file)
+        for r, k in zip(rows, self._kpts_host[si, : len(rows)].reshape(len(rows), -1).tolist()):
+            r["keypoints"] = k
+        return rows
+
+    def _save_txt(self, pred, si, shape, file):
+        """save_one_txt (val.py:226-236): the keypoints behind each box."""
+        from .results import Results
+
+        Results(None, path=None, names=self.model.names, boxes=pred[:, :6], orig_shape=(shape[0], shape[1]),
+                keypoints=self._kpts_host[si, : len(pred)].clone()).save_txt(
+                    file, save_conf=bool(self.args.get("save_conf", False)))
+
+    def get_desc(self):
+        """pose/val.py:47-62 with this fork's mAP75 column in both groups."""
+        return ("%22s" + "%11s" * 12) % ("Class", "Images", "Instances", "Box(P", "R", "mAP50", "mAP75", "mAP50-95)",
+                                         "Pose(P", "R", "mAP50", "mAP75", "mAP50-95)")
 
 
 def pred_to_json(predn: torch.Tensor, filename, class_map=None) -> list:

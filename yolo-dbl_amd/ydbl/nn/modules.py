@@ -1733,6 +1733,99 @@ def seg_coefficients(mcs) -> torch.Tensor:
     return torch.cat([v.torch().reshape(v.n, v.h * v.w, v.c) for v in mcs], 1).permute(0, 2, 1).contiguous()
 
 
+def emit_conv_padded(plan: Plan, m: "Conv", x: TV, c_pad: int) -> TV:
+    """A Conv whose output channel count is no multiple of 8, carried at c_pad = round_up(c, 8) channels so that the
+    next dense conv reads whole 16-byte channel vectors: the extra output channels get zero weight rows and zero bias,
+    and SiLU(0) = 0, so they are exact zeros.  m's input may itself be such a padded map (emit_dense's ci < x.c)."""
+    conv = m.conv
+    assert conv.groups == 1 and conv.out_channels <= c_pad and isinstance(m.act, (nn.SiLU, nn.Identity))
+    w, b = m.folded()
+    co = conv.out_channels
+    if b is None:
+        b = torch.zeros(co)
+    w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 0, 0, c_pad - co))
+    b = torch.nn.functional.pad(b, (0, c_pad - co))
+    k, s, p, d = conv.kernel_size[0], conv.stride[0], conv.padding[0], conv.dilation[0]
+    ho, wo = conv_out_hw(x.h, x.w, k, s, p, d)
+    y = plan.alloc(x.n, ho, wo, c_pad)
+    emit_dense(plan, x, y, w, b, s, p, d, _act_code(m.act), what=f"Conv{k}x{k}.pad{c_pad}")
+    return y
+
+
+class Pose(Detect):
+    """U/nn/modules/head.py:328-401 — Detect plus the keypoint branch: per level cv4 = Conv3x3 -> Conv3x3 -> Conv2d 1x1
+    giving nk = K * ndim raw keypoint values per anchor.  They go into a buffer of their own per level
+    ([B, h, w, nk]), so the level buffers [B, h, w, 64 + nc] keep their layout and the boxes equal the detection
+    model's.  emit() returns the Detect levels and leaves ``plan.pose = [keypoint views]``; the kept rows' keypoints
+    are decoded behind the NMS by ydbl_pose_keypoints (tail.NmsTail).  c4 = max(ch[0] // 4, nk) need not be a multiple
+    of 8 (51 at scales n and s): the two 3x3 intermediates are then carried zero-padded (emit_conv_padded)."""
+
+    def __init__(self, nc: int = 80, kpt_shape: tuple = (17, 3), ch: tuple = (), legacy: bool | None = None):
+        super().__init__(nc, ch, legacy)
+        self.kpt_shape = kpt_shape
+        self.nk = kpt_shape[0] * kpt_shape[1]
+        c4 = max(ch[0] // 4, self.nk)
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, self.nk, 1)) for x in ch)
+
+    def emit(self, plan, xs, out=None):
+        levels = self._emit_branches(plan, xs, self.cv2, self.cv3)
+        kpts = []
+        for i, x in enumerate(xs):
+            c4 = self.cv4[i][0].conv.out_channels
+            if c4 % 8:
+                t = emit_conv_padded(plan, self.cv4[i][0], x, round_up(c4, 8))
+                t = emit_conv_padded(plan, self.cv4[i][1], t, round_up(c4, 8))
+            else:
+                t = emit_conv3x3_pair(plan, self.cv4[i][0], self.cv4[i][1], x)
+            kpts.append(emit_conv2d(plan, self.cv4[i][2], t, plan.alloc(x.n, x.h, x.w, self.nk), what="Pose.kpt"))
+        plan.pose = kpts
+        return levels
+
+    def _forward_plan(self, plan, xs):
+        """forward(x) in inference mode (head.py:364-372 with export False): (cat([y, pred_kpt], 1) [B, 4+nc+nk, A],
+        (feats, kpt [B, nk, A])) as fresh tensors of the plan's dtype; kpts_decode in torch, as the reference's."""
+        det = super()._forward_plan(plan, xs)
+        kpts, strides = plan.pose, self.stride.tolist()
+
+        def finish():
+            y, feats = det()
+            kpt = pose_raw(kpts).to(y.dtype)
+            return torch.cat([y, kpts_decode(kpt, kpts, strides, self.kpt_shape[1])], 1), (feats, kpt)
+
+        return finish
+
+
+def pose_raw(kpts) -> torch.Tensor:
+    """The per-level raw keypoint views [B, h, w, nk] as the reference's kpt [B, nk, A] (head.py:367), a fresh tensor."""
+    return torch.cat([v.torch().reshape(v.n, v.h * v.w, v.c) for v in kpts], 1).permute(0, 2, 1).contiguous()
+
+
+def pose_grid(kpts, strides, device):
+    """(gx [A], gy [A], stride [A]) fp32 of the anchors of the levels `kpts` (views or (h, w) pairs), level after
+    level, row-major: make_anchors' points minus 0.5 (U/utils/tal.py:317-330)."""
+    gx, gy, st = [], [], []
+    for v, s in zip(kpts, strides):
+        h, w = (v.h, v.w) if hasattr(v, "h") else v
+        yy, xx = torch.meshgrid(torch.arange(h, dtype=torch.float32, device=device),
+                                torch.arange(w, dtype=torch.float32, device=device), indexing="ij")
+        gx.append(xx.reshape(-1))
+        gy.append(yy.reshape(-1))
+        st.append(torch.full((h * w,), float(s), dtype=torch.float32, device=device))
+    return torch.cat(gx), torch.cat(gy), torch.cat(st)
+
+
+def kpts_decode(kpt: torch.Tensor, kpts, strides, ndim: int) -> torch.Tensor:
+    """Pose.kpts_decode (head.py:396-401) of kpt [B, nk, A] in kpt's dtype, in torch: the parity surface of
+    ``model(x)``, not the hot path (ydbl_pose_keypoints decodes the kept rows)."""
+    gx, gy, st = (t.to(kpt.dtype) for t in pose_grid(kpts, strides, kpt.device))
+    y = kpt.clone()
+    if ndim == 3:
+        y[:, 2::3] = y[:, 2::3].sigmoid()
+    y[:, 0::ndim] = (y[:, 0::ndim] * 2.0 + gx) * st
+    y[:, 1::ndim] = (y[:, 1::ndim] * 2.0 + gy) * st
+    return y
+
+
 def emit_module(m: nn.Module, plan: Plan, x, out=None):
     """Emit any parsed layer: built-in modules (HIP launches), nn.Sequential repeats, and registered plugin
     classes that only have a torch forward (emit_torch)."""

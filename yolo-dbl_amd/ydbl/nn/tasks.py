@@ -39,13 +39,13 @@ REGISTRY: dict[str, type] = {
               M.GhostBottleneck, M.DSBottleneck, M.DSC3k, M.DSC3k2, M.HyperACE, M.DownsampleConv,
               M.FullPAD_Tunnel, M.DySample, M.LSKblock, M.Detect, M.AAttn, M.ABlock, M.A2C2f, M.SPPF, M.C3k, M.C3k2,
               M.Attention, M.PSABlock, M.C2PSA, M.PSA, M.SCDown, M.RepVGGDW, M.CIB, M.C2fCIB, M.v10Detect, M.Proto,
-              M.Segment)
+              M.Segment, M.Pose)
 }
 REGISTRY["nn.Upsample"] = M.Upsample  # the one torch.nn layer name the v13 YAMLs use (U/nn/tasks.py:972-973)
 _C1C2 = {"Conv", "DWConv", "GhostConv", "Bottleneck", "GhostBottleneck", "C2f", "C3", "C3Ghost", "DSC3k2", "DSConv",
          "DSBottleneck", "A2C2f", "SPPF", "C3k2", "C2PSA", "PSA", "SCDown", "C2fCIB"}
 _REPEAT_ARG = {"C2f", "C3", "C3Ghost", "DSC3k2", "A2C2f", "C3k2", "C2PSA", "C2fCIB"}
-_DETECT = {"Detect", "v10Detect", "Segment"}  # U/nn/tasks.py:1107-1112
+_DETECT = {"Detect", "v10Detect", "Segment", "Pose"}  # U/nn/tasks.py:1107-1112
 _C1_ONLY = {"DySample", "LSKblock"}
 
 
@@ -149,7 +149,7 @@ def parse_model(d: dict, ch: int = 3, verbose: bool = False):
         if name not in REGISTRY:
             raise KeyError(f"module '{name}' (layer {i}) has no MI355X implementation")
         m = REGISTRY[name]
-        args = [nc if a == "nc" else a for a in args]
+        args = [nc if a == "nc" else d.get("kpt_shape") if a == "kpt_shape" else a for a in args]
         for j, a in enumerate(args):  # YAML delivers 'None' as a string (U/nn/tasks.py:1000-1003)
             if isinstance(a, str):
                 with contextlib.suppress(ValueError, SyntaxError):
@@ -197,7 +197,7 @@ def parse_model(d: dict, ch: int = 3, verbose: bool = False):
             args = [c1, *args[1:]]
         else:
             c2 = ch[f]
-        if name in ("Detect", "Segment"):
+        if name in ("Detect", "Segment", "Pose"):
             m.legacy = legacy  # class attribute, as the reference sets it (U/nn/tasks.py:1111-1112)
             m_ = m(*args)
             m_.legacy = legacy  # and on the instance: a yolov8 (legacy) and a yolo11 model may live in one process
@@ -220,18 +220,25 @@ def parse_model(d: dict, ch: int = 3, verbose: bool = False):
 class DetectionModel(nn.Module):
     """U/nn/tasks.py:313-359 + BaseModel.fuse (:207-235)."""
 
-    def __init__(self, cfg="yolov13n_DBL.yaml", ch=3, nc=None, verbose=False):
+    def __init__(self, cfg="yolov13n_DBL.yaml", ch=3, nc=None, verbose=False, data_kpt_shape=(None, None)):
         super().__init__()
         self.yaml = cfg if isinstance(cfg, dict) else yaml_model_load(cfg)
         ch = self.yaml["ch"] = self.yaml.get("ch", ch)
         if nc and nc != self.yaml["nc"]:
             self.yaml["nc"] = nc
+        # PoseModel.__init__ (U/nn/tasks.py): the dataset's kpt_shape overrides the config's
+        if data_kpt_shape is not None and any(data_kpt_shape) and "kpt_shape" in self.yaml \
+                and list(data_kpt_shape) != list(self.yaml["kpt_shape"]):
+            self.yaml["kpt_shape"] = list(data_kpt_shape)
         self.model, self.save = parse_model(deepcopy(self.yaml), ch=ch, verbose=verbose)
         self.names = {i: f"{i}" for i in range(self.yaml["nc"])}
         self.inplace = self.yaml.get("inplace", True)
         m = self.model[-1]
         self.end2end = bool(getattr(m, "end2end", False))  # U/nn/tasks.py:331
         self.segment = isinstance(m, M.Segment)  # SegmentationModel (U/nn/tasks.py:439-452): the same forward
+        self.pose = isinstance(m, M.Pose)  # PoseModel: the same forward, the head also returns the keypoints
+        if self.pose:
+            self.kpt_shape = list(m.kpt_shape)
         # Stride probe by shape propagation at 256x256 (the reference runs a train-mode forward on
         # zeros, U/nn/tasks.py:337-350; only its output shapes are used for the strides).
         s = 256
@@ -294,7 +301,7 @@ class DetectionModel(nn.Module):
             if augment:
                 warn_e2e_augment()
             return self._run(x, e2e=True)[1]
-        if self.segment and augment:  # _predict_augment (U/nn/tasks.py:361-366): any class but DetectionModel
+        if (self.segment or self.pose) and augment:  # _predict_augment (U/nn/tasks.py:361-366): any class but DetectionModel
             warn_no_augment()
             augment = False
         s, _ = self._run(x, augment=augment)
@@ -305,6 +312,10 @@ class DetectionModel(nn.Module):
         if self.segment:  # Segment.forward (U/nn/modules/head.py:259-271): (cat([y, mc], 1), (feats, mc, p))
             mc, p = s.seg_outputs()
             return torch.cat([y, mc], 1), (feats, mc, p)
+        if self.pose:  # Pose.forward (U/nn/modules/head.py:364-372): (cat([y, pred_kpt], 1), (feats, kpt))
+            kpt = s.pose_outputs()
+            views = s.parts[0].compiled.plan.pose
+            return torch.cat([y, M.kpts_decode(kpt, views, self.stride.tolist(), self.kpt_shape[1])], 1), (feats, kpt)
         return y, feats
 
     MAX_LABELS = 300  # per image: the capacity of the in-graph loss's label buffer (loss(batch) with preds=None)
@@ -575,6 +586,8 @@ def check_e2e_loss(model):
     any device work."""
     if getattr(model, "segment", False):
         raise NotImplementedError("the loss of a segmentation model is v8SegmentationLoss, which is not implemented")
+    if getattr(model, "pose", False):
+        raise NotImplementedError("the loss of a pose model is v8PoseLoss, which is not implemented")
     if getattr(model, "end2end", False):
         raise NotImplementedError("the loss of an end2end (YOLOv10) model is E2EDetectLoss (one2many + one2one "
                                   "assignment), which is not implemented")

@@ -14,7 +14,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import DecodeDesc, NmsDesc, TopkDesc, View
+from ._lib import DecodeDesc, NmsDesc, PoseKptDesc, TopkDesc, View
 from .runtime import Plan
 
 # Score threshold from which the NMS runs one workgroup per image instead of the class-split sweep (ydbl_nms_desc
@@ -73,7 +73,7 @@ class _Tail:
     lists ``cands`` and the ``classes`` filter as a device tensor."""
 
     fused = sparse = False  # (NmsTail: the candidates come from the class-conv tails / the sparse box path runs)
-    keep_idx = None
+    keep_idx = kpts = None
 
     def __init__(self, plan: Plan, batch: int, A: int, head, opt, det, count, pred, multi_label: bool):
         dev = plan.device
@@ -111,15 +111,23 @@ class _Tail:
 class NmsTail(_Tail):
     """Decode + ydbl_nms: cap = A candidates per image (x nc multi-label), the ``classes`` filter in the decode, the
     NMS workspace zero-filled once (include/ydbl.h) and, for a Segment head, ``keep_idx`` [B, max_det]: per kept row
-    the candidate's index, which finds its mask coefficients (ydbl_nms_desc.out_idx)."""
+    the candidate's index, which finds its mask coefficients (ydbl_nms_desc.out_idx).  A Pose head (pose=True) gets
+    ``keep_idx`` too, and ``kpts`` [B, max_det, K, ndim] fp32 (or the caller's view): the kept rows' keypoints, decoded
+    by one ydbl_pose_keypoints launch behind the NMS (emit_keypoints)."""
 
-    def __init__(self, plan: Plan, batch: int, A: int, head, opt, det, count, pred=None, segment=False):
+    def __init__(self, plan: Plan, batch: int, A: int, head, opt, det, count, pred=None, segment=False, pose=False,
+                 kpts=None):
         super().__init__(plan, batch, A, head, opt, det, count, pred, bool(opt.multi_label) and head.nc > 1)
         self.ws = nms_workspace(batch, self.cap, opt.max_nms, plan.device)
         plan.buffers.append(self.ws)
-        if segment:
+        if segment or pose:
             self.keep_idx = torch.full((batch, self.max_det), -1, dtype=torch.int32, device=plan.device)
             plan.buffers.append(self.keep_idx)
+        if pose:
+            K, ndim = head.kpt_shape
+            self.kpts = kpts if kpts is not None else torch.zeros((batch, self.max_det, K, ndim), dtype=torch.float32,
+                                                                  device=plan.device)
+            plan.buffers.append(self.kpts)
 
     def emit_decode(self, levels) -> DecodeDesc:
         """The candidates of one compiled forward, whose launches are already in the plan.  No decode pass when every
@@ -150,6 +158,19 @@ class NmsTail(_Tail):
         self._emit_select("ydbl_nms", "NMS", NmsDesc, h, w, iou_thres=float(opt.iou), max_nms=int(opt.max_nms),
                           agnostic=int(bool(opt.agnostic)), max_wh=float(opt.max_wh),
                           out_idx=self.keep_idx.data_ptr() if self.keep_idx is not None else None)
+
+    def emit_keypoints(self, views):
+        """ydbl_pose_keypoints behind emit_nms: the raw keypoint maps `views` (plan.pose) at the anchors keep_idx
+        names -> ``kpts`` (slots past the count zeroed).  nms=False: nothing to decode."""
+        if not self.opt.nms:
+            return
+        h = self.head
+        K, ndim = h.kpt_shape
+        assert self.kpts.is_contiguous() and self.count.stride(0) == 1
+        d = PoseKptDesc((View * 3)(*[v.struct() for v in views]), len(views), h.nc if self.multi_label else 0,
+                        (C.c_float * 3)(*[float(s) for s in h.stride.tolist()]), self.keep_idx.data_ptr(),
+                        self.count.data_ptr(), self.batch, self.max_det, K, ndim, self.kpts.data_ptr())
+        self.plan.launch("ydbl_pose_keypoints", d, what="Pose.keypoints", keep=[d])
 
     def fuse_candidates(self, levels, dd: DecodeDesc) -> bool:
         """Point the candidate sinks of the plan's class-conv tail launches (include/ydbl.h, ydbl_dsconv_desc) at the

@@ -397,6 +397,41 @@ class SegmentMetrics:
         return d
 
 
+# The COCO keypoint evaluation's per-keypoint scales (nose, eyes, ears, shoulders, elbows, wrists, hips, knees, ankles),
+# U/utils/metrics.py:15-18: the published COCO sigmas.
+OKS_SIGMA = np.array([0.26, 0.25, 0.25, 0.35, 0.35, 0.79, 0.79, 0.72, 0.72, 0.62, 0.62, 1.07, 1.07, 0.87, 0.87, 0.89,
+                      0.89]) / 10.0
+
+
+def kpt_iou(kpt1, kpt2, area, sigma, eps=1e-7):
+    """U/utils/metrics.py:156-175 (OKS): kpt1 [N, K, 3] ground truth, kpt2 [M, K, >= 2] predictions, area [N], sigma
+    [K] -> [N, M], in torch on the tensors' device and dtype.  (The validator's batch form is ydbl_kpt_oks.)"""
+    d = (kpt1[:, None, :, 0] - kpt2[..., 0]).pow(2) + (kpt1[:, None, :, 1] - kpt2[..., 1]).pow(2)
+    sigma = torch.as_tensor(np.asarray(sigma), device=kpt1.device).to(kpt1.dtype)
+    kpt_mask = kpt1[..., 2] != 0
+    e = d / ((2 * sigma).pow(2) * (area[:, None, None] + eps) * 2)
+    return ((-e).exp() * kpt_mask[:, None]).sum(-1) / (kpt_mask.sum(-1)[:, None] + eps)
+
+
+class PoseMetrics(SegmentMetrics):
+    """U/utils/metrics.py:1051-1165 with this fork's mAP75 in both groups, as SegmentMetrics: ``box`` and ``pose`` are
+    BoxMetric, fitness = pose + box."""
+
+    keys = [*DetMetrics.keys, "metrics/precision(P)", "metrics/recall(P)", "metrics/mAP50(P)", "metrics/mAP75(P)",
+            "metrics/mAP50-95(P)"]
+    curves = [*DetMetrics.curves, "Precision-Recall(P)", "F1-Confidence(P)", "Precision-Confidence(P)",
+              "Recall-Confidence(P)"]
+
+    def __init__(self, names=None):
+        super().__init__(names)
+        self.pose = self.seg  # the second group under its own name (the shared methods read self.seg)
+        self.task = "pose"
+
+    def process(self, tp, tp_p, conf, pred_cls, target_cls):
+        """:1096-1131: keypoints first, then boxes, each through ap_per_class."""
+        super().process(tp, tp_p, conf, pred_cls, target_cls)
+
+
 class ConfusionMatrix:
     """U/utils/metrics.py:294-445 for detection, counted on the device by ydbl_confusion_matrix.
 

@@ -57,6 +57,63 @@ def scale_boxes(img1_shape, boxes, img0_shape, ratio_pad=None, padding=True, xyw
     return clip_boxes(boxes, img0_shape)
 
 
+def clip_coords(coords, shape):
+    """U/utils/ops.py:341-358: x to [0, shape[1]], y to [0, shape[0]], in place (tensor or ndarray)."""
+    if isinstance(coords, torch.Tensor):
+        coords[..., 0] = coords[..., 0].clamp(0, shape[1])
+        coords[..., 1] = coords[..., 1].clamp(0, shape[0])
+    else:
+        coords[..., 0] = coords[..., 0].clip(0, shape[1])
+        coords[..., 1] = coords[..., 1].clip(0, shape[0])
+    return coords
+
+
+def scale_coords(img1_shape, coords, img0_shape, ratio_pad=None, normalize=False, padding=True):
+    """U/utils/ops.py:740-772: point coordinates (x, y in the first two columns) from the letterboxed img1_shape to
+    img0_shape, in place.  Unlike scale_boxes the pad is NOT rounded."""
+    if ratio_pad is None:
+        gain = min(img1_shape[0] / img0_shape[0], img1_shape[1] / img0_shape[1])
+        pad = (img1_shape[1] - img0_shape[1] * gain) / 2, (img1_shape[0] - img0_shape[0] * gain) / 2
+    else:
+        gain = ratio_pad[0][0]
+        pad = ratio_pad[1]
+    if padding:
+        coords[..., 0] -= pad[0]
+        coords[..., 1] -= pad[1]
+    coords[..., 0] /= gain
+    coords[..., 1] /= gain
+    coords = clip_coords(coords, img0_shape)
+    if normalize:
+        coords[..., 0] /= img0_shape[1]
+        coords[..., 1] /= img0_shape[0]
+    return coords
+
+
+def kpt_oks(pred_kpts, count, gt_kpts, gt_box, gt_ofs, sigma, stream=None):
+    """One ydbl_kpt_oks launch (include/ydbl.h): pred_kpts fp32 [B, max_det, K, ndim] and count int32 [B] (a
+    session's kpts / count, or copies brought to the labels' space) against gt_kpts fp32 [n_gt, K, 3] with the label
+    boxes gt_box fp32 [n_gt, 4] xyxy, grouped by gt_ofs int32 [B + 1]; sigma fp32 [K]; all on the device.
+    -> oks fp32 [n_gt, max_det] (row g: label g against the slots of its own image; columns >= count are 0)."""
+    dev = pred_kpts.device
+    n, max_det, K, ndim = pred_kpts.shape
+    n_gt = gt_kpts.shape[0]
+    for t, dt in ((pred_kpts, torch.float32), (gt_kpts, torch.float32), (gt_box, torch.float32),
+                  (sigma, torch.float32), (count, torch.int32), (gt_ofs, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise ValueError("kpt_oks: contiguous fp32 / int32 tensors on one device expected")
+    if tuple(gt_kpts.shape[1:]) != (K, 3) or tuple(gt_box.shape) != (n_gt, 4) or sigma.numel() != K \
+            or count.numel() != n or gt_ofs.numel() != n + 1:
+        raise ValueError("kpt_oks: gt_kpts [n_gt, K, 3], gt_box [n_gt, 4], sigma [K], count [B], gt_ofs [B + 1] expected")
+    oks = torch.empty((max(n_gt, 1), max_det), dtype=torch.float32, device=dev)
+    d = _lib.KptOksDesc(pred_kpts.data_ptr(), count.data_ptr(), n, max_det, K, ndim,
+                        gt_kpts.data_ptr() if n_gt else None, gt_box.data_ptr() if n_gt else None, gt_ofs.data_ptr(),
+                        n_gt, sigma.data_ptr(), oks.data_ptr())
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(_lib.lib.ydbl_kpt_oks(d, stream), "ydbl_kpt_oks")
+    return oks[:n_gt]
+
+
 def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False,
                         multi_label=False, labels=(), max_det=300, nc=0, max_time_img=0.05, max_nms=30000,
                         max_wh=7680, in_place=True, rotated=False):
